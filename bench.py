@@ -6,21 +6,28 @@ Default workload (--config c3): one "step" = one full routing build of the
 U[0,0.01], self-loops, seed 3), from the CSR resident in HBM to the n x n
 (latency, loss) table resident in HBM (all-gathered on every rank for N > 1):
 the latency closure plus the exact-loss pass.  value = n^2 pairs / step time.
-Beside it the line carries the end-to-end build through the C ABI
+A plain run does that and no more: set up, warm up, time the steps, print the
+line.  With --full the line also carries the end-to-end build through the C ABI
 (srt_compute_shortest_paths: host CSR in, srt_path[n*n] in the caller's host
-buffer out, every validation and PCIe copy included) -- BASELINE.md's t_build.
+buffer out, every validation and PCIe copy included) -- BASELINE.md's t_build --
+the cold first calls in fresh processes, the CPU baselines, and at N > 1 the
+no-exchange share and the one-process t_build; c5 adds its event push.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(the table's latency_ns / packet_loss rows named in rows.npy and its
+min_latency_ns; c5: the round's flags and deliver_ns, the packet counters and
+stats); the inputs are seeded, so two builds can be compared output for output.
 
 Other configs (same JSON shape):
   --config c1   1,000-node complete graph through its GML TEXT: parse + build +
-                fetch to the host per step; the reference CPU path (faithful
-                restatement, all sources) is timed in full beside it
+                fetch to the host per step; with --full the reference CPU path
+                (faithful restatement, all sources) is timed in full beside it
   --config c2   4,096-node complete graph (blocked Floyd-Warshall, 1 GPU)
   --config c2nc the C2 graph with 30% of its edges dropped (dense, not complete:
                 key width from the eccentricity proof)
   --config c4   100,000-node Barabasi-Albert graph, m=4 (batched sparse sweep)
   --config c5   1M packets/round send_packet decision on the C1 table (packets/s)
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--full] [--dump-outputs DIR]
 Multi-GPU: one rank per GPU (RCCL), launched by torch.distributed.run; run as
 `python bench.py --gpus N` without a launcher it starts the N ranks itself
 (before any GPU call) and exits with their status.  Prints one JSON line on
@@ -84,6 +91,14 @@ def parse_args():
     ap.add_argument("--in-use", dest="in_use", type=int, default=0,
                     help="c4: number of in-use nodes (default: all)")
     ap.add_argument("--seed", type=int, default=-1)
+    ap.add_argument("--full", action="store_true", default=False,
+                    help="also measure what the headline figure does not need: the CPU baselines, the end-to-end "
+                         "C ABI builds and the cold first calls (fresh processes), the no-exchange share and the "
+                         "one-process t_build at N > 1, c5's event push (each can be dropped again with its --no-* "
+                         "option); without --full the line carries null in their places")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(float32 / float64; tables over the size budget as a fixed, seeded sample of whole rows)")
     ap.add_argument("--cpu-baseline", dest="cpu_baseline", action="store_true", default=True)
     ap.add_argument("--no-cpu-baseline", dest="cpu_baseline", action="store_false")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = the CPUs this process may use")
@@ -96,8 +111,8 @@ def parse_args():
     ap.add_argument("--exchange", default="auto", choices=["auto", "none", "allgather"],
                     help="N > 1: 'allgather' (the default, 'auto') = the communicator-bound build the north_star "
                          "names: rows all-gathered over RCCL so every rank holds the whole table (the line's value; "
-                         "the no-exchange share is measured after it and carried as config.no_exchange); 'none' = "
-                         "LEVEL / SSSP rows sharded with no collective as the value (each rank's rows stay in its HBM)")
+                         "with --full the no-exchange share is measured after it and carried as config.no_exchange); "
+                         "'none' = LEVEL / SSSP rows sharded with no collective as the value (each rank's rows stay in its HBM)")
     ap.add_argument("--tbuild-child", dest="tbuild_child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--algo", default="auto", choices=["auto", "fw", "sssp", "level"],
                     help="kernel family (default: AUTO, the library's priced choice -- what the drop-in runs)")
@@ -109,7 +124,48 @@ def parse_args():
                     help="measurement only (dense FW, 1 GPU): time one rank of an N-rank run -- 1/N of the "
                          "block-rows plus the pivot owner's chain every round, no collectives; the table "
                          "is not valid and no bench line is printed, only the timing")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.cpu_baseline = args.e2e = args.cold = False
+    return args
+
+
+DUMP_BUDGET = 48 << 20  # bytes of .npy a --dump-outputs run writes at most (tables beyond it: sampled rows)
+
+
+def dump_outputs(args, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy, integers as float64 (exact
+    below 2^53: latencies in ns, counters, flags), float32 kept."""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a))
+
+
+def sample_rows(n_rows, row_bytes, seed, first=0):
+    """The table rows a dump carries: all of them when they fit DUMP_BUDGET,
+    else a sorted sample that depends on the seed and the sizes only."""
+    k = int(max(1, min(n_rows, DUMP_BUDGET // max(row_bytes, 1))))
+    if k == n_rows:
+        return np.arange(first, first + n_rows, dtype=np.int64)
+    return first + np.sort(np.random.default_rng(seed).choice(n_rows, k, replace=False)).astype(np.int64)
+
+
+def plan_table_rows(plan, rows, dev):
+    """Rows of the plan's table in HBM (srt_plan_table: u64 latency_ns and f32
+    packet_loss, n x n each), copied to the host."""
+    import torch
+
+    from shadow_amd.dist import _CudaBuf
+    lat_p, loss_p, n = plan.table_ptrs()
+    d = torch.device("cuda", dev)
+    idx = torch.from_numpy(rows).to(d)
+    lat = torch.as_tensor(_CudaBuf(lat_p, n * n * 8), device=d).view(torch.int64).view(n, n)
+    loss = torch.as_tensor(_CudaBuf(loss_p, n * n * 4), device=d).view(torch.float32).view(n, n)
+    return lat.index_select(0, idx).cpu().numpy().view(np.uint64), loss.index_select(0, idx).cpu().numpy()
 
 
 def cpu_share():
@@ -296,11 +352,12 @@ def timed_builds(plan, D, steps, warmup):
 ALGOS = {"auto": 0, "fw": 1, "sssp": 2, "level": 3}
 
 
-def e2e_build(g, nodes, reps=3, algo=0):
+def e2e_build(g, nodes, reps=3, algo=0, keep=None):
     """BASELINE.md t_build: srt_compute_shortest_paths from the host CSR to the
     srt_path table in the caller's (pre-touched, reused) host buffer -- plan
     creation and validation, the CSR upload, the build, the download -- as the
-    Rust shim would call it.  Best of `reps` calls."""
+    Rust shim would call it.  Best of `reps` calls.  keep (a list): receives
+    the host table and the min latency of the last call."""
     from shadow_amd import _lib
 
     L = _lib.lib()
@@ -321,6 +378,8 @@ def e2e_build(g, nodes, reps=3, algo=0):
         _lib.check(rc, err)
         best = dt if best is None else min(best, dt)
         times.append(round(dt * 1e3, 2))
+    if keep is not None:
+        keep[:] = [out, mn.value]
     return {"ms": best * 1e3, "pairs_per_s": n * n / best, "calls": reps, "call_ms": times,
             "first_call_note": "the process's first call also pins the 192 MB download staging (behind its closure) "
                                "and cannot use the piece-pipelined upload, which needs that staging",
@@ -471,9 +530,11 @@ def bench_gml(args, cfg, D):
     text = gml_graph(n_nodes, seed)
     nodes = np.arange(n_nodes, dtype=np.uint32)
 
+    last = []  # the last step's host table
+
     def step():
         g = NetworkGraph.parse(text)
-        return e2e_build(g, nodes, reps=1)
+        return e2e_build(g, nodes, reps=1, keep=last)
 
     for _ in range(args.warmup):
         step()
@@ -483,6 +544,11 @@ def bench_gml(args, cfg, D):
         step()
     D.barrier()
     elapsed = D.max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and D.rank == 0:
+        table = last[0].reshape(n_nodes, n_nodes)
+        rows = sample_rows(n_nodes, n_nodes * 12, seed)
+        dump_outputs(args, {"rows": rows, "latency_ns": table["lat"][rows], "packet_loss": table["loss"][rows],
+                            "min_latency_ns": np.array([last[1]], np.uint64)})
     out = None
     if D.rank == 0:
         per = elapsed / args.steps
@@ -620,10 +686,17 @@ def bench_graph(args, cfg, D):
     timing = plan.timing()  # phase breakdown of the last timed build
     desc = plan.describe()  # after the runs: the first one adds what it measured (e.g. sym=triangle)
     plan.fetch(table=False)  # connectivity check + min latency (not timed)
-    plan.close()
     n = len(nodes)
+    if args.dump_outputs and D.rank == 0:
+        # the table in HBM as srt_plan_table hands it to the caller; a row-sharded plan wrote its own rows only
+        r0, r1 = (D.rank * n // ranks, (D.rank + 1) * n // ranks) if " shard=" in desc else (0, n)
+        rows = sample_rows(r1 - r0, n * 12, seed, first=r0)
+        d_lat, d_loss = plan_table_rows(plan, rows, D.dev)
+        dump_outputs(args, {"rows": rows, "latency_ns": d_lat, "packet_loss": d_loss,
+                            "min_latency_ns": np.array([plan.min_latency_ns], np.uint64)})
+    plan.close()
     no_exchange = None
-    if D.world > 1 and transport is not None and desc.startswith(("level", "sssp")):
+    if args.full and D.world > 1 and transport is not None and desc.startswith(("level", "sssp")):
         # the same build with rows sharded and no collective (each rank's rows
         # stay in its HBM): what the exchange costs, carried beside the value
         p2 = RoutingPlan(g, nodes, algo=ALGOS[args.algo], device=D.dev)
@@ -861,27 +934,42 @@ def bench_packets(args, cfg, D):
     D.barrier()
     elapsed = D.max_over_ranks(time.perf_counter() - t0)
     dev_ms = ev0.elapsed_time(ev1) / args.steps
-    # the round's event push (srt_packet_events, worker.rs:629-639), timed
-    # after the headline loop on the last round's flags: reported beside the
-    # decision rate, not folded into it
-    dst_host = ((pk["dst_row"].astype(np.int64) + n_nodes * (np.arange(n_pkts) % max(1, hosts // n_nodes)))
-                % hosts).astype(np.int32)
-    t_dh = torch.from_numpy(dst_host).to(dev)
-    t_base = torch.zeros(hosts, dtype=torch.int64, device=dev)
-    t_eid = torch.zeros(n_pkts, dtype=torch.int64, device=dev)
-    t_ord = torch.zeros(n_pkts, dtype=torch.int32, device=dev)
-    t_ptr = torch.zeros(hosts + 1, dtype=torch.int32, device=dev)
-    ev_reps = max(3, args.steps)
-    plan.packet_events(t_hp, t_f, t_d, t_dh, hosts, t_base, t_eid, t_ord, t_ptr)
-    ee0, ee1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    te0 = time.perf_counter()
-    ee0.record(stream)
-    for _ in range(ev_reps):  # asynchronous calls, one status check at the end
-        plan.packet_events(t_hp, t_f, t_d, t_dh, hosts, t_base, t_eid, t_ord, t_ptr, check=False)
-    ee1.record(stream)
-    plan.packet_events_status()
-    events_ms = (time.perf_counter() - te0) * 1e3 / ev_reps
-    events_dev_ms = ee0.elapsed_time(ee1) / ev_reps
+    if args.dump_outputs and D.rank == 0:
+        # the last round's decisions; the per-pair counters and the min-combined stats accumulate over every
+        # round run (warmup included), so they depend on --steps and --warmup as well
+        arrays = {"flags": t_f.cpu().numpy(), "deliver_ns": t_d.cpu().numpy(),
+                  "stats": t_s.cpu().numpy().view(np.uint64)}
+        if t_cc is not None:
+            arrays["packet_counts"] = t_cc.cpu().numpy()
+        dump_outputs(args, arrays)
+    events = None
+    if args.full:
+        # the round's event push (srt_packet_events, worker.rs:629-639), timed
+        # after the headline loop on the last round's flags: reported beside the
+        # decision rate, not folded into it
+        dst_host = ((pk["dst_row"].astype(np.int64) + n_nodes * (np.arange(n_pkts) % max(1, hosts // n_nodes)))
+                    % hosts).astype(np.int32)
+        t_dh = torch.from_numpy(dst_host).to(dev)
+        t_base = torch.zeros(hosts, dtype=torch.int64, device=dev)
+        t_eid = torch.zeros(n_pkts, dtype=torch.int64, device=dev)
+        t_ord = torch.zeros(n_pkts, dtype=torch.int32, device=dev)
+        t_ptr = torch.zeros(hosts + 1, dtype=torch.int32, device=dev)
+        ev_reps = max(3, args.steps)
+        plan.packet_events(t_hp, t_f, t_d, t_dh, hosts, t_base, t_eid, t_ord, t_ptr)
+        ee0, ee1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        te0 = time.perf_counter()
+        ee0.record(stream)
+        for _ in range(ev_reps):  # asynchronous calls, one status check at the end
+            plan.packet_events(t_hp, t_f, t_d, t_dh, hosts, t_base, t_eid, t_ord, t_ptr, check=False)
+        ee1.record(stream)
+        plan.packet_events_status()
+        events = {"ms_per_round": (time.perf_counter() - te0) * 1e3 / ev_reps,
+                  "device_ms_per_round": ee0.elapsed_time(ee1) / ev_reps,
+                  "sent": int(t_ptr[-1].item()),
+                  "what": "srt_packet_events on the round's sent packets: per-host event ids, stable sort by "
+                          "destination, deliver times sorted within each destination (the queue pop order); "
+                          "asynchronous calls, wall clock per round with one status check at the end, and the "
+                          "device time of the same calls"}
     out = None
     if D.rank == 0:
         per_round = elapsed / args.steps
@@ -921,12 +1009,7 @@ def bench_packets(args, cfg, D):
                          "device_ms_per_round": dev_ms,
                          "basis": "52 B/packet + 64 B/host (SURVEY.md 8(d))"},
             "cpu_baseline": cpu,
-            "events": {"ms_per_round": events_ms, "device_ms_per_round": events_dev_ms,
-                       "sent": int(t_ptr[-1].item()),
-                       "what": "srt_packet_events on the round's sent packets: per-host event ids, stable sort by "
-                               "destination, deliver times sorted within each destination (the queue pop order); "
-                               "asynchronous calls, wall clock per round with one status check at the end, and the "
-                               "device time of the same calls"},
+            "events": events,
         }
     plan.close()
     return out

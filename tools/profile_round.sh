@@ -12,7 +12,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-timeout -k 10 400 python -u bench.py "$@" > $O/bench.json 2> $O/bench.err; rc=$?
+timeout -k 10 400 python -u bench.py "$@" --full > $O/bench.json 2> $O/bench.err; rc=$?
 echo "bench rc=$rc"; tail -1 $O/bench.json | cut -c1-400; [ $rc -eq 0 ] || exit $rc
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 $R/bench.py "$@" --no-cpu-baseline --no-e2e --no-cold > $O/trace.log 2>&1; rc=$?
