@@ -31,9 +31,11 @@
 #include <thread>
 #include <vector>
 
+#include "srt_choose.h"
 #include "srt_internal.h"
 #include "srt_scan.h"
 
+using srt::CreateKnobs;
 using srt::CsrStats;
 using srt::KeyParams;
 using srt::csr_scan;
@@ -148,11 +150,10 @@ struct PieceUpload {
     bool on = false;
     bool check_loss = true;
 
-    bool init(const srt_csr *g_, CsrStats *cs, bool check_loss_) {
+    bool init(const srt_csr *g_, CsrStats *cs, bool check_loss_, const srt::Knob<int> &piece) {
         g = g_;
         check_loss = check_loss_;
-        const char *pe = std::getenv("SRT_UPLOAD_PIECE");
-        if (pe) PE = 1ull << std::max(4, std::min(24, std::atoi(pe)));
+        if (piece.set) PE = 1ull << std::max(4, std::min(24, piece.v));
         else if (g->n_adj < PE) return false;
         const uint32_t V = g->n_nodes;
         cut.push_back(0);
@@ -344,71 +345,6 @@ struct LossUpload {
         return st;
     }
 };
-
-// Choose the closure's key representation and prove it exact.
-//
-// Keys are path latencies in units of g = gcd of all edge latencies (latency
-// only: the loss is recomputed exactly by the loss pass, so no loss bits share
-// the key).  Lmax bounds every shortest-path latency: the longest edge for a
-// complete graph (a direct edge bounds every pair), else (V-1) * max edge --
-// or, tighter, in-eccentricity + out-eccentricity of one node that reaches
-// and is reached by every node (fw_ecc_bound: d(u,v) <= d(u,s) + d(s,v)).
-// Edges longer than Lmax are then stored saturated at INF (the init kernels).
-// Exactness does not depend on the schedule's read order: (1) every stored
-// value only decreases from its initial value <= INF, so each operand is <=
-// INF and a candidate (sum of two) is <= 2 INF, which the key type holds
-// without wrapping (u16 lanes: 0xFFFE; u32: 2^32 - 2) -- no candidate is ever
-// corrupted, whatever the grouped / look-ahead / sharded schedules read; (2) a
-// candidate below INF is the exact length of a real walk, so no stored value
-// drops below the true distance d; (3) the schedule's values are never above
-// the sequential Floyd-Warshall's (its candidates are formed from operands at
-// least as tight), which ends at d.  So the closure ends at d exactly when
-// every finite d < INF -- Lmax < INF.  The test below asks for 2 Lmax + 1 <
-// INF, a margin kept from the r01 packed (latency, loss) keys.  Below 2^53 the
-// keys may be f64 (v_add_f64 / v_min_f64), below 2^62 u64, and below
-// KEY32_INF (2^31 - 1) u32; u16 below KEY16_INF.  Lmax < 2^32 - 1
-// additionally lets the loss pass keep latencies as u32.  Knob
-// SRT_FW_KEY=u32|f64|u64 (measurement / A-B parity only) skips the narrower
-// representations.
-bool choose_key_params(const CsrStats &cs, uint32_t V, uint64_t ecc_units, KeyParams *kp, int *key_type, bool *f16,
-                       std::string *why) {
-    kp->g = cs.gcd;
-    const uint64_t maxu = cs.maxlat / cs.gcd;
-    unsigned __int128 Lmax = cs.complete ? (unsigned __int128)maxu : (unsigned __int128)(V ? V - 1 : 0) * maxu;
-    // the eccentricity bound (fw_ecc_bound), when the sweeps found one
-    if (ecc_units != ~0ull && (unsigned __int128)ecc_units < Lmax) Lmax = ecc_units;
-    kp->lmax = Lmax > (unsigned __int128)~0ull ? ~0ull : (uint64_t)Lmax;
-    kp->lat32 = Lmax < 0xffffffffull;
-    // knob SRT_FW_KEY = u16 / u32 / f64 / u64: the narrowest key allowed (A/B, tests)
-    const char *force = std::getenv("SRT_FW_KEY");
-    const bool allow16 = !force || std::strcmp(force, "u16") == 0;
-    const int min_type = !force ? srt::KEY_U32 : std::strcmp(force, "u64") == 0 ? srt::KEY_U64
-                         : std::strcmp(force, "f64") == 0 ? srt::KEY_F64 : srt::KEY_U32;
-    *f16 = false;
-    if (allow16 && 2 * Lmax + 1 < (unsigned __int128)srt::KEY16_INF) {
-        *key_type = srt::KEY_U16;
-        // f16 integer arithmetic on the same 2-byte keys (0.75 VALU slot per
-        // relaxation instead of 1): every finite distance < 1024 = F16 INF,
-        // so candidates stay <= 2048, exact in f16 (srt_fw.hip).  SRT_FW_KEY=u16
-        // keeps integer arithmetic (A/B parity tests).
-        *f16 = !force && Lmax < 1024;
-        return true;
-    }
-    if (min_type <= srt::KEY_U32 && 2 * Lmax + 1 < (unsigned __int128)srt::KEY32_INF) {
-        *key_type = srt::KEY_U32;
-        return true;
-    }
-    if (min_type <= srt::KEY_F64 && 2 * Lmax + 1 < ((unsigned __int128)1 << 53)) {
-        *key_type = srt::KEY_F64;
-        return true;
-    }
-    if (2 * Lmax + 1 < ((unsigned __int128)1 << 62)) {
-        *key_type = srt::KEY_U64;
-        return true;
-    }
-    *why = "the latency range does not fit a 62-bit exact key";
-    return false;
-}
 
 // Teardown of the one-call builds' plans behind their return (C3: ~6 ms of
 // stream syncs and hipFree of ~5 GB): one worker thread, plans queued; an
@@ -631,217 +567,6 @@ void free_plan_buffers(srt_plan *p) {
     if (p->h_tcount) hipHostFree(p->h_tcount);
 }
 
-// Sparse SSSP key (srt_sssp.hip): latency in units of g in the high 32 bits.
-// A stored value is a simple path (<= V-1 edges) and a candidate adds one
-// edge, so V * max_edge_latency / g < 2^32 - 1 keeps every sum exact and
-// below the all-ones "unreached" key.
-bool sssp_params(const CsrStats &cs, uint32_t V, std::string *why) {
-    if ((unsigned __int128)V * (cs.maxlat / cs.gcd) >= 0xffffffffull) {
-        *why = "V * max edge latency exceeds the 32-bit latency field of the SSSP key";
-        return false;
-    }
-    return true;
-}
-
-// Family prices for AUTO, seconds on one MI355X, from the measured rates of
-// DESIGN.md 4 (rest launches by key type, r03 profiles; sparse builds r04).
-// Dense: Vp^3 relaxations (half on the triangle schedule: 2-byte keys on a
-// symmetric graph), at least ~80 us a 128-pivot round (the chain: C2 4k), plus
-// the exact-loss fold (C3: 7.0 ms for 16k x 16k pairs).  Sparse: one unit per
-// (source, in-edge or vertex) visited, at the C4 rate of the frontier sweeps
-// (u16 latencies) or of the packed-key sweeps, at least ~1 ms a launch of
-// sources (its ~60 dependent sweeps).
-double price_fw(uint32_t Vp, uint32_t n, uint32_t V, int key_type, bool f16, bool sym) {
-    const double rate = f16                          ? 4.3e13   // C3 rest: 1.45 ms / 6.26e10
-                        : key_type == srt::KEY_U16 ? 3.3e13     // 1.90 ms (r02)
-                        : key_type == srt::KEY_U32 ? 1.25e13    // 4.82-5.19 ms
-                        : key_type == srt::KEY_F64 ? 8e12       // ~half the u32 mix, not profiled
-                                                   : 4e12;      // u64: ~1/3 of u32's mix, not profiled
-    const bool tri = sym && (f16 || key_type == srt::KEY_U16);
-    const double relax = (double)Vp * Vp * Vp * (tri ? 0.5 : 1.0);
-    return std::max(relax / rate, (double)(Vp / 128) * 80e-6) + (double)n * V * 2.6e-11;
-}
-// Level solve: a row walks the probe row's edge count plus ~4 passes over
-// the row's V levels (init, the level collections), at the level fold's
-// measured cost per visit (C3: 4.56 ms for 16k rows of ~160k visits), and
-// writes its 12-byte table row.
-double price_level(uint32_t n, uint32_t V, uint64_t visits) {
-    return (double)n * ((double)visits + 4.0 * V) * 1.8e-12 + (double)n * n * 12.0 / 5e12 + 3e-4;
-}
-double price_sparse(uint32_t n, uint64_t n_in, uint32_t V, bool frontier) {
-    const double units = (double)n * ((double)n_in + V);
-    const double per = frontier ? 1.19e-11 : 1.73e-11;  // C4: 9e10 units in 1.07 s / 1.56 s
-    const double launches = std::ceil((double)n / (frontier ? 8192.0 : 4096.0));
-    return std::max(units * per, launches * 1e-3);
-}
-
-// Pull-form adjacency for the sweep: for every v, the entries u -> v of every
-// row u (petgraph edges(u): directed outgoing / undirected incident), minus
-// self-loops (they never shorten a path; the diagonal is the raw self-loop).
-void build_in_edges(const srt_csr *g, uint64_t gunit, uint64_t n_in, std::vector<uint64_t> *ptr,
-                    std::vector<srt::InEdge> *edges) {
-    const uint32_t V = g->n_nodes;
-    ptr->assign((size_t)V + 1, 0);
-    for (uint32_t u = 0; u < V; ++u)
-        for (uint64_t k = g->row_ptr[u]; k < g->row_ptr[u + 1]; ++k)
-            if (g->col[k] != u) (*ptr)[g->col[k] + 1]++;
-    for (uint32_t v = 0; v < V; ++v) (*ptr)[v + 1] += (*ptr)[v];
-    edges->resize(std::max<uint64_t>(n_in, 1));
-    std::vector<uint64_t> fill(ptr->begin(), ptr->end() - 1);
-    for (uint32_t u = 0; u < V; ++u)
-        for (uint64_t k = g->row_ptr[u]; k < g->row_ptr[u + 1]; ++k) {
-            const uint32_t v = g->col[k];
-            if (v == u) continue;
-            srt::InEdge e;
-            e.u = u;
-            e.w = (uint32_t)(g->lat_ns[k] / gunit);
-            e.eb = 1.0f - g->loss[k];
-            e.pad = 0;
-            (*edges)[fill[v]++] = e;
-        }
-}
-
-// Is the latency adjacency symmetric (every u -> v of latency w has a v -> u of
-// latency w, as multisets -- petgraph undirected graphs are)?  Then every
-// shortest latency is symmetric, L(s, v) = L(v, s), which the frontier sweeps
-// use to seed a launch from the rows of the earlier ones.  Per vertex: the
-// in-edges (u, w) against the out-row (col, lat / g), both sorted; host threads
-// over vertex ranges.
-bool latency_symmetric(const srt_csr *g, const std::vector<uint64_t> &in_ptr, const std::vector<srt::InEdge> &in_edge,
-                       uint64_t gunit) {
-    const uint32_t V = g->n_nodes;
-    const unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    std::vector<uint8_t> bad(nt, 0);
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; ++t)
-        th.emplace_back([&, t] {
-            std::vector<uint64_t> a, b;
-            for (uint32_t v = (uint32_t)((uint64_t)V * t / nt); v < (uint32_t)((uint64_t)V * (t + 1) / nt) && !bad[t];
-                 ++v) {
-                a.clear();
-                b.clear();
-                for (uint64_t k = in_ptr[v]; k < in_ptr[v + 1]; ++k)
-                    a.push_back((uint64_t)in_edge[k].u << 32 | in_edge[k].w);
-                for (uint64_t k = g->row_ptr[v]; k < g->row_ptr[v + 1]; ++k)
-                    if (g->col[k] != v) b.push_back((uint64_t)g->col[k] << 32 | (uint32_t)(g->lat_ns[k] / gunit));
-                if (a.size() != b.size()) {
-                    bad[t] = 1;
-                    break;
-                }
-                std::sort(a.begin(), a.end());
-                std::sort(b.begin(), b.end());
-                if (a != b) bad[t] = 1;
-            }
-        });
-    for (auto &x : th) x.join();
-    for (uint8_t x : bad)
-        if (x) return false;
-    return true;
-}
-
-// Source order of the sparse sweeps: the level order of a shortest-latency
-// tree from the highest-degree vertex (then from the lowest-numbered vertex
-// not yet reached): the root, its tree children, theirs, ... each parent's
-// children together.  The sweeps put table rows in this order into their
-// words, lanes (8 sources) and 128-B lines (32 sources); sources at the same
-// tree depth under nearby parents reach most targets along paths of the same
-// hop count, so a word's labels change at the same vertices in the same
-// sweeps.  C4's graph (tools measurement on the host, hop counts of the
-// shortest-path trees of 32-source lines over all targets): 3.1 distinct hop
-// counts a line in this order, 9.7 in plain breadth-first order from the same
-// root, 7.5 in tree depth-first order.  Measured on C4: loss sweeps 266 -> 214
-// ms a build; but as the order of the launches (which sources come first) it
-// costs the symmetric seeding (latency sweeps 94 -> 142 ms), so the frontier
-// composes launches in breadth-first order (hop_rank) and orders rows within a
-// launch by this rank.
-// plain breadth-first discovery order from the same root (knob SRT_SSSP_ORDER=2, A/B)
-std::vector<uint32_t> hop_rank(const srt_csr *g) {
-    const uint32_t V = g->n_nodes;
-    std::vector<uint32_t> rank(V, ~0u), q;
-    q.reserve(V);
-    uint32_t start = 0;
-    uint64_t best = 0;
-    for (uint32_t u = 0; u < V; ++u)
-        if (g->row_ptr[u + 1] - g->row_ptr[u] > best) best = g->row_ptr[u + 1] - g->row_ptr[u], start = u;
-    uint32_t next = 0;
-    for (uint32_t root = start, scan = 0; next < V;) {
-        if (rank[root] == ~0u) {
-            rank[root] = next++;
-            q.push_back(root);
-            for (size_t h = q.size() - 1; h < q.size(); ++h)
-                for (uint64_t k = g->row_ptr[q[h]]; k < g->row_ptr[q[h] + 1]; ++k) {
-                    const uint32_t v = g->col[k];
-                    if (v < V && rank[v] == ~0u) {
-                        rank[v] = next++;
-                        q.push_back(v);
-                    }
-                }
-        }
-        while (scan < V && rank[scan] != ~0u) ++scan;
-        root = scan;
-    }
-    return rank;
-}
-
-std::vector<uint32_t> spt_rank(const srt_csr *g) {
-    const uint32_t V = g->n_nodes, NONE = ~0u;
-    std::vector<uint32_t> rank(V, NONE), first(V, NONE), last(V, NONE), sib(V, NONE), q;
-    std::vector<uint64_t> dist(V, ~0ull);
-    std::vector<uint32_t> pred(V, NONE);
-    std::vector<uint8_t> done(V, 0);
-    q.reserve(V);
-    uint32_t start = 0;
-    uint64_t best = 0;
-    for (uint32_t u = 0; u < V; ++u)
-        if (g->row_ptr[u + 1] - g->row_ptr[u] > best) best = g->row_ptr[u + 1] - g->row_ptr[u], start = u;
-    typedef std::pair<uint64_t, uint32_t> Item;
-    std::priority_queue<Item, std::vector<Item>, std::greater<Item>> heap;
-    uint32_t next = 0;
-    for (uint32_t root = start, scan = 0; next < V;) {
-        if (rank[root] == NONE) {
-            // Dijkstra over the adjacency's latencies; a vertex joins its
-            // parent's child list when settled (children in settle order)
-            dist[root] = 0;
-            heap.push({0, root});
-            while (!heap.empty()) {
-                const Item it = heap.top();
-                heap.pop();
-                const uint32_t u = it.second;
-                if (done[u] || it.first != dist[u]) continue;
-                done[u] = 1;
-                if (u != root) {
-                    const uint32_t pu = pred[u];
-                    if (last[pu] == NONE) first[pu] = u;
-                    else sib[last[pu]] = u;
-                    last[pu] = u;
-                }
-                for (uint64_t k = g->row_ptr[u]; k < g->row_ptr[u + 1]; ++k) {
-                    const uint32_t v = g->col[k];
-                    if (v >= V || done[v]) continue;
-                    const uint64_t d = it.first + g->lat_ns[k];
-                    if (d < dist[v]) {
-                        dist[v] = d;
-                        pred[v] = u;
-                        heap.push({d, v});
-                    }
-                }
-            }
-            // the tree's level order
-            q.clear();
-            q.push_back(root);
-            rank[root] = next++;
-            for (size_t h = 0; h < q.size(); ++h)
-                for (uint32_t c = first[q[h]]; c != NONE; c = sib[c]) {
-                    rank[c] = next++;
-                    q.push_back(c);
-                }
-        }
-        while (scan < V && rank[scan] != NONE) ++scan;
-        root = scan;
-    }
-    return rank;
-}
-
 }  // namespace
 
 extern "C" {
@@ -865,39 +590,100 @@ srt_status srt_plan_create(const srt_csr *g, const uint32_t *nodes, uint32_t n,
 }
 
 namespace {
-// defer_loss (end-to-end build only): the edge-loss array is uploaded by
-// run_tail, while the closure runs -- g->loss must stay valid until then
-srt_status plan_create_impl(const srt_csr *g, const uint32_t *nodes, uint32_t n, const srt_opts *opts,
-                            srt_plan **plan_out, srt_err *err, bool defer_loss) {
-    clear_err(err);
-    srt::init_wait();  // a pending srt_init_async finishes before any device work
-    // plans an earlier one-call build queued for teardown free their HBM
-    // before this plan sizes itself (hipMemGetInfo) or allocates anything
-    reap_drain();
+
+// The environment variables of plan creation (srt_choose.h CreateKnobs), read
+// at the start of every create: they may change between two plans of one
+// process.
+void read_create_knobs(CreateKnobs &k) {
+    const auto read = [](const char *name, auto &knob, auto parse) {
+        if (const char *e = std::getenv(name)) {
+            knob.set = true;
+            knob.v = parse(e);
+        }
+    };
+    const auto as_int = [](const char *e) { return std::atoi(e); };
+    const auto as_ll = [](const char *e) { return std::atoll(e); };
+    k.fw_no_ecc = std::getenv("SRT_FW_NO_ECC") != nullptr;
+    read("SRT_LEVEL", k.level, as_int);
+    read("SRT_LVL_SYM", k.lvl_sym, as_int);
+    read("SRT_LEVEL_Q", k.level_q, as_int);
+    read("SRT_FW_P1", k.fw_p1, as_int);
+    read("SRT_FW_EMULATE_RANKS", k.fw_emulate_ranks, as_int);
+    read("SRT_FW_BAND", k.fw_band, [](const char *e) { return e[0] == '1'; });
+    read("SRT_FW_KEY", k.fw_key, [](const char *e) -> int {
+        return std::strcmp(e, "u16") == 0 ? srt::KEY_U16 : std::strcmp(e, "u64") == 0 ? srt::KEY_U64
+               : std::strcmp(e, "f64") == 0 ? srt::KEY_F64 : srt::KEY_U32;
+    });
+    read("SRT_SSSP_KEY", k.sssp_key, as_int);
+    read("SRT_SSSP_ORDER", k.sssp_order, as_int);
+    read("SRT_SSSP_DELTA", k.sssp_delta, [](const char *e) { return std::atof(e); });
+    read("SRT_SSSP_ACT", k.sssp_act, as_int);
+    read("SRT_SSSP_FR_NB", k.sssp_fr_nb, as_ll);
+    read("SRT_SSSP_FR_GRID", k.sssp_fr_grid, as_int);
+    read("SRT_SSSP_SYM", k.sssp_sym, as_int);
+    read("SRT_FR_FIRST", k.fr_first, as_ll);
+    read("SRT_UPLOAD_PIECE", k.upload_piece, as_int);
+}
+
+// a plan under construction: destroyed unless create releases it to the caller
+struct PlanDelete {
+    void operator()(srt_plan *p) const { srt_plan_destroy(p); }
+};
+
+// What the stages of plan creation share.  defer_loss (end-to-end build only):
+// the edge-loss array is uploaded by run_tail, while the closure runs --
+// g->loss must stay valid until then.
+struct Create {
+    const srt_csr *g;
+    const uint32_t *nodes;
+    uint32_t n;
+    const srt_opts *opts;
+    srt_err *err;
+    bool defer_loss;
+    srt_plan *p = nullptr;
+    uint32_t want = SRT_ALGO_AUTO;  // srt_opts.algo
+    CreateKnobs knobs;
+    CsrStats cs;
+    uint64_t n_in = 0;             // adjacency entries that are no self-loop
+    srt_err derr{};                // the device set-up's error, reported behind the reference's
+    uint64_t ecc_units = ~0ull;    // the eccentricity proof's bound, units of g (~0: none)
+    uint64_t lvl_bound = ~0ull, lvl_visits = 0;  // the level probe's
+    bool fw_ok = false, sssp_ok = false, f16 = false;
+    std::string why_fw, why_sssp, auto_note;
+    std::vector<uint64_t> sl_lat;  // the in-use nodes' self-loops
+    std::vector<float> sl_loss;
     Trace tr;
-    if (!g || !plan_out || (n && !nodes) || !g->row_ptr || (g->n_adj && (!g->col || !g->lat_ns || !g->loss))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+};
+
+#define ST_TRY(expr)                          \
+    do {                                      \
+        const srt_status st_ = (expr);        \
+        if (st_ != SRT_OK) return st_;        \
+    } while (0)
+
+srt_status refuse(srt_err *err, srt_status s, const char *msg) {
+    set_err(err, s, msg);
+    return s;
+}
+
+// argument checks; in-use nodes must be valid and unique (they come from a HashSet)
+srt_status check_arguments(const srt_csr *g, const uint32_t *nodes, uint32_t n, srt_plan **plan_out, srt_err *err) {
+    if (!g || !plan_out || (n && !nodes) || !g->row_ptr || (g->n_adj && (!g->col || !g->lat_ns || !g->loss)))
+        return refuse(err, SRT_ERR_INVALID, "null argument");
     *plan_out = nullptr;
-    // in-use nodes must be valid and unique (they come from a HashSet)
     std::vector<uint8_t> seen(g->n_nodes, 0);
     for (uint32_t i = 0; i < n; ++i) {
-        if (nodes[i] >= g->n_nodes || seen[nodes[i]]) {
-            set_err(err, SRT_ERR_INVALID, "in-use node list has an out-of-range or duplicate NodeIndex");
-            return SRT_ERR_INVALID;
-        }
+        if (nodes[i] >= g->n_nodes || seen[nodes[i]])
+            return refuse(err, SRT_ERR_INVALID, "in-use node list has an out-of-range or duplicate NodeIndex");
         seen[nodes[i]] = 1;
     }
-    if (g->row_ptr[g->n_nodes] != g->n_adj) {
-        set_err(err, SRT_ERR_INVALID, "row_ptr[n_nodes] != n_adj");
-        return SRT_ERR_INVALID;
-    }
+    if (g->row_ptr[g->n_nodes] != g->n_adj) return refuse(err, SRT_ERR_INVALID, "row_ptr[n_nodes] != n_adj");
+    return SRT_OK;
+}
+
+srt_plan *new_plan(const srt_csr *g, const uint32_t *nodes, uint32_t n) {
     srt_plan *p = new (std::nothrow) srt_plan();
-    if (!p) {
-        set_err(err, SRT_ERR_OOM, "out of host memory");
-        return SRT_ERR_OOM;
-    }
+    if (!p) return nullptr;
     p->V = g->n_nodes;
     p->Vp = ((g->n_nodes + srt::FW_B - 1) / srt::FW_B) * srt::FW_B;
     if (p->Vp == 0) p->Vp = srt::FW_B;
@@ -906,283 +692,269 @@ srt_status plan_create_impl(const srt_csr *g, const uint32_t *nodes, uint32_t n,
     p->n = n;
     p->n_adj = g->n_adj;
     p->nodes.assign(nodes, nodes + n);
-    p->identity_nodes = (n == g->n_nodes);
-    for (uint32_t i = 0; i < n && p->identity_nodes; ++i) p->identity_nodes = nodes[i] == i;
     if (g->node_ids) p->node_ids.assign(g->node_ids, g->node_ids + g->n_nodes);
+    return p;
+}
 
-    // 1. the CSR scan (validation + statistics) on host threads while this
-    //    thread sets up the device and uploads the CSR
-    CsrStats cs;
-    PieceUpload pu;
-    const bool piped = pu.init(g, &cs, !defer_loss);
-    std::thread scanner;
-    if (!piped) scanner = std::thread([&] { csr_scan(g, &cs, !defer_loss); });
-    srt_err derr{};
-    const srt_status dst = [&]() -> srt_status {
-        srt_err *err = &derr;
-        int dev = opts && opts->device >= 0 ? opts->device : -1;
-        if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-        p->device = dev;
-        hipError_t e = hipSetDevice(dev);
-        if (e != hipSuccess) return hip_fail(err, e, "hipSetDevice");
-        p->own_stream = true;
-        if (!take_stream_set(dev, p)) {
-            e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-            if (e != hipSuccess) return hip_fail(err, e, "hipStreamCreate");
-            int lo = 0, hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-            e = hipStreamCreateWithPriority(&p->side_stream, hipStreamNonBlocking, hi);
-            if (e == hipSuccess) e = hipStreamCreateWithPriority(&p->comm_stream, hipStreamNonBlocking, hi);
-            if (e != hipSuccess) return hip_fail(err, e, "hipStreamCreateWithPriority");
-            (void)hipEventCreate(&p->ev_begin);
-            (void)hipEventCreate(&p->ev_end);
-            // the stream-to-stream events of the look-ahead schedule (the
-            // system-scope fence is kept: skipping it measured no faster)
-            const unsigned sync_fl = hipEventDisableTiming;
-            (void)hipEventCreateWithFlags(&p->ev_cross, sync_fl);
-            (void)hipEventCreateWithFlags(&p->ev_pivot, sync_fl);
-            (void)hipEventCreateWithFlags(&p->ev_row, sync_fl);
-            (void)hipEventCreateWithFlags(&p->ev_bcast, sync_fl);
-        }
-        tr.mark("create: streams + events");
-        srt_status st;
-        if ((st = dmalloc(&p->d_row_ptr, (size_t)g->n_nodes + 1, err)) != SRT_OK ||
-            (st = dmalloc(&p->d_col, g->n_adj, err)) != SRT_OK || (st = dmalloc(&p->d_lat, g->n_adj, err)) != SRT_OK ||
-            (st = dmalloc(&p->d_loss, g->n_adj, err)) != SRT_OK || (st = dmalloc(&p->d_nodes, n, err)) != SRT_OK ||
-            (st = dmalloc(&p->d_sl_lat, n, err)) != SRT_OK || (st = dmalloc(&p->d_sl_loss, n, err)) != SRT_OK ||
-            (st = dmalloc(&p->d_stats, 2, err)) != SRT_OK || (st = dmalloc(&p->d_rstats, 2, err)) != SRT_OK)
-            return st;
-        tr.mark("create: CSR device buffers");
-        auto up = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
-            if (!bytes) return hipSuccess;
-            return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, p->stream);
-        };
-        if (defer_loss) p->h_loss_defer = g->loss;
-        if ((e = up(p->d_row_ptr, g->row_ptr, ((size_t)g->n_nodes + 1) * 8)) != hipSuccess ||
-            (e = up(p->d_nodes, nodes, (size_t)n * 4)) != hipSuccess ||
-            (e = piped ? hipSuccess : up(p->d_col, g->col, g->n_adj * 4)) != hipSuccess ||
-            (e = piped ? hipSuccess : up(p->d_lat, g->lat_ns, g->n_adj * 8)) != hipSuccess)
-            return hip_fail(err, e, "upload");
-        if (piped && (st = pu.run(p, err)) != SRT_OK) return st;
-        if ((e = defer_loss ? hipSuccess : up(p->d_loss, g->loss, g->n_adj * 4)) != hipSuccess)
-            return hip_fail(err, e, "upload");
-        return SRT_OK;
-    }();
-    tr.mark(piped ? "create: device setup+piece upload" : "create: device setup+upload");
-    if (piped) pu.finish(&cs);
-    else scanner.join();
-    p->ident_rows = cs.ident;
-    {
-        bool idn = n == g->n_nodes;
-        for (uint32_t j = 0; idn && j < n; ++j) idn = nodes[j] == j;
-        p->ident_nodes = idn;
+// the device, its streams and events, the CSR's device buffers and its upload
+// (the pieces of `pu` when the piece pipeline is on); errors go to c.derr
+srt_status setup_device(Create &c, PieceUpload *pu) {
+    srt_plan *p = c.p;
+    const srt_csr *g = c.g;
+    const uint32_t n = c.n;
+    srt_err *err = &c.derr;
+    int dev = c.opts && c.opts->device >= 0 ? c.opts->device : -1;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
+    p->device = dev;
+    hipError_t e = hipSetDevice(dev);
+    if (e != hipSuccess) return hip_fail(err, e, "hipSetDevice");
+    p->own_stream = true;
+    if (!take_stream_set(dev, p)) {
+        e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+        if (e != hipSuccess) return hip_fail(err, e, "hipStreamCreate");
+        int lo = 0, hi = 0;
+        (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+        e = hipStreamCreateWithPriority(&p->side_stream, hipStreamNonBlocking, hi);
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&p->comm_stream, hipStreamNonBlocking, hi);
+        if (e != hipSuccess) return hip_fail(err, e, "hipStreamCreateWithPriority");
+        (void)hipEventCreate(&p->ev_begin);
+        (void)hipEventCreate(&p->ev_end);
+        // the stream-to-stream events of the look-ahead schedule (the
+        // system-scope fence is kept: skipping it measured no faster)
+        const unsigned sync_fl = hipEventDisableTiming;
+        (void)hipEventCreateWithFlags(&p->ev_cross, sync_fl);
+        (void)hipEventCreateWithFlags(&p->ev_pivot, sync_fl);
+        (void)hipEventCreateWithFlags(&p->ev_row, sync_fl);
+        (void)hipEventCreateWithFlags(&p->ev_bcast, sync_fl);
     }
-    tr.mark("create: CSR scan (joined)");
-
-    // 2. the reference's errors, in its order: edge attributes (parse time),
-    //    then the self-loop of every in-use node in node order (mod.rs:210-217)
-    auto fail = [&](srt_status s, const char *msg) {
-        srt_plan_destroy(p);
-        set_err(err, s, msg);
-        return s;
+    c.tr.mark("create: streams + events");
+    ST_TRY(dmalloc(&p->d_row_ptr, (size_t)g->n_nodes + 1, err));
+    ST_TRY(dmalloc(&p->d_col, g->n_adj, err));
+    ST_TRY(dmalloc(&p->d_lat, g->n_adj, err));
+    ST_TRY(dmalloc(&p->d_loss, g->n_adj, err));
+    ST_TRY(dmalloc(&p->d_nodes, n, err));
+    ST_TRY(dmalloc(&p->d_sl_lat, n, err));
+    ST_TRY(dmalloc(&p->d_sl_loss, n, err));
+    ST_TRY(dmalloc(&p->d_stats, 2, err));
+    ST_TRY(dmalloc(&p->d_rstats, 2, err));
+    c.tr.mark("create: CSR device buffers");
+    auto up = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
+        if (!bytes) return hipSuccess;
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, p->stream);
     };
-    if (cs.badcol_k != ~0ull) return fail(SRT_ERR_INVALID, "adjacency entry names a node out of range");
-    if (cs.zero_k != ~0ull) return fail(SRT_ERR_INVALID, "Edge 'latency' must not be 0");
-    if (cs.badloss_k != ~0ull) return fail(SRT_ERR_INVALID, "Edge 'packet_loss' is not in the range [0,1]");
-    std::vector<uint64_t> sl_lat(n);
-    std::vector<float> sl_loss(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t u = nodes[i], c = cs.sl_cnt[u];
-        if (c != 1) {
-            // the losses were left to the device: the parse-time error first
-            if (defer_loss && srt::first_bad_loss(g) != ~0ull)
-                return fail(SRT_ERR_INVALID, "Edge 'packet_loss' is not in the range [0,1]");
-            srt_plan_destroy(p);
-            return edge_error(err, (int)c, node_id(g, u), node_id(g, u));
-        }
-        sl_lat[i] = g->lat_ns[cs.sl_first[u]];
-        sl_loss[i] = g->loss[cs.sl_first[u]];
-    }
-    if (dst != SRT_OK) {
-        srt_plan_destroy(p);
-        if (err) *err = derr;
-        return dst;
-    }
+    if (c.defer_loss) p->h_loss_defer = g->loss;
+    if ((e = up(p->d_row_ptr, g->row_ptr, ((size_t)g->n_nodes + 1) * 8)) != hipSuccess ||
+        (e = up(p->d_nodes, c.nodes, (size_t)n * 4)) != hipSuccess ||
+        (e = pu ? hipSuccess : up(p->d_col, g->col, g->n_adj * 4)) != hipSuccess ||
+        (e = pu ? hipSuccess : up(p->d_lat, g->lat_ns, g->n_adj * 8)) != hipSuccess)
+        return hip_fail(err, e, "upload");
+    if (pu) ST_TRY(pu->run(p, err));
+    if ((e = c.defer_loss ? hipSuccess : up(p->d_loss, g->loss, g->n_adj * 4)) != hipSuccess)
+        return hip_fail(err, e, "upload");
+    return SRT_OK;
+}
 
-    // the kernels of creation (bound proofs, probes, symmetry check) are
-    // timed from here on (srt::cspan_*): srt_timing.create_device_ms.  The
-    // code objects are loaded first (once per device and process; srt_init
-    // does it ahead of time), so a span holds no lazy load of a kernel.
-    {
-        static std::mutex mu;
-        static std::vector<int> loaded;
-        std::lock_guard<std::mutex> lk(mu);
-        if (std::find(loaded.begin(), loaded.end(), p->device) == loaded.end()) {
-            (void)hipSetDevice(p->device);
-            if (srt::preload_kernels() == hipSuccess) loaded.push_back(p->device);
+// 1. the CSR scan (validation + statistics) on host threads while this
+//    thread sets up the device and uploads the CSR.  The scan is joined before
+//    the return; the status is the device set-up's (its error in c.derr).
+srt_status scan_beside_device_setup(Create &c) {
+    srt_plan *p = c.p;
+    PieceUpload pu;
+    const bool piped = pu.init(c.g, &c.cs, !c.defer_loss, c.knobs.upload_piece);
+    std::thread scanner;
+    if (!piped) scanner = std::thread([&] { csr_scan(c.g, &c.cs, !c.defer_loss); });
+    const srt_status dst = setup_device(c, piped ? &pu : nullptr);
+    c.tr.mark(piped ? "create: device setup+piece upload" : "create: device setup+upload");
+    if (piped) pu.finish(&c.cs);
+    else scanner.join();
+    p->ident_rows = c.cs.ident;
+    bool idn = c.n == c.g->n_nodes;
+    for (uint32_t j = 0; idn && j < c.n; ++j) idn = c.nodes[j] == j;
+    p->ident_nodes = idn;
+    c.n_in = c.g->n_adj - c.cs.selfloops;
+    c.tr.mark("create: CSR scan (joined)");
+    return dst;
+}
+
+// 2. the reference's errors, in its order: edge attributes (parse time),
+//    then the self-loop of every in-use node in node order (mod.rs:210-217);
+//    only then an error of the device set-up (dst)
+srt_status reference_errors(Create &c, srt_status dst) {
+    const srt_csr *g = c.g;
+    const CsrStats &cs = c.cs;
+    if (cs.badcol_k != ~0ull) return refuse(c.err, SRT_ERR_INVALID, "adjacency entry names a node out of range");
+    if (cs.zero_k != ~0ull) return refuse(c.err, SRT_ERR_INVALID, "Edge 'latency' must not be 0");
+    if (cs.badloss_k != ~0ull) return refuse(c.err, SRT_ERR_INVALID, "Edge 'packet_loss' is not in the range [0,1]");
+    c.sl_lat.resize(c.n);
+    c.sl_loss.resize(c.n);
+    for (uint32_t i = 0; i < c.n; ++i) {
+        const uint32_t u = c.nodes[i], cnt = cs.sl_cnt[u];
+        if (cnt != 1) {
+            // the losses were left to the device: the parse-time error first
+            if (c.defer_loss && srt::first_bad_loss(g) != ~0ull)
+                return refuse(c.err, SRT_ERR_INVALID, "Edge 'packet_loss' is not in the range [0,1]");
+            return edge_error(c.err, (int)cnt, node_id(g, u), node_id(g, u));
         }
+        c.sl_lat[i] = g->lat_ns[cs.sl_first[u]];
+        c.sl_loss[i] = g->loss[cs.sl_first[u]];
+    }
+    if (dst != SRT_OK && c.err) *c.err = c.derr;
+    return dst;
+}
+
+// The kernels of creation (bound proofs, probes, symmetry check) are timed
+// from here on (srt::cspan_*): srt_timing.create_device_ms.  The code objects
+// are loaded first (once per device and process; srt_init does it ahead of
+// time), so a span holds no lazy load of a kernel.
+void open_create_timing(srt_plan *p) {
+    static std::mutex mu;
+    static std::vector<int> loaded;
+    std::lock_guard<std::mutex> lk(mu);
+    if (std::find(loaded.begin(), loaded.end(), p->device) == loaded.end()) {
+        (void)hipSetDevice(p->device);
+        if (srt::preload_kernels() == hipSuccess) loaded.push_back(p->device);
     }
     p->in_create = true;
-    auto dev_timed = [&](auto &&fn) -> srt_status { return fn(); };
+}
 
-    // 2b. the key-width proof from the real diameter, where the family is
-    //     likely dense, the graph is not complete (complete graphs have the
-    //     longest-edge bound) and (V-1) * max edge would not allow f16 keys
-    uint64_t ecc_units = ~0ull;
-    uint32_t ecc_sweeps = 0;
-    {
-        const uint64_t maxu = cs.maxlat / cs.gcd;
-        const uint64_t nin = g->n_adj - cs.selfloops;
-        const uint32_t want0 = opts ? opts->algo : (uint32_t)SRT_ALGO_AUTO;
-        // priced as if the proof gave 2-byte keys (it decides whether to run it)
-        const bool sym = cs.sym_a == cs.sym_b;
-        const bool dense_likely = want0 == SRT_ALGO_FW ||
-                                  (want0 == SRT_ALGO_AUTO && price_fw(p->Vp, n, p->V, srt::KEY_U16, true, sym) <
-                                                                 price_sparse(n, nin, p->V, true));
-        // sparse plans need it too: the frontier sweeps keep u16 latencies
-        // when every finite distance is below 0xFFFF units (srt_frontier.hip)
-        const bool sparse_u16 = !dense_likely && (unsigned __int128)(p->V ? p->V - 1 : 0) * maxu >= 0xffff;
-        if (!cs.complete && (dense_likely || sparse_u16) &&
-            (unsigned __int128)(p->V ? p->V - 1 : 0) * maxu >= 1024 && !std::getenv("SRT_FW_NO_ECC")) {
-            uint64_t b = ~0ull;
-            srt_err e2{};
-            if (dev_timed([&] { return srt::fw_ecc_bound(p, 512, &b, &ecc_sweeps, &e2); }) != SRT_OK) {
-                srt_plan_destroy(p);
-                if (err) *err = e2;
-                return SRT_ERR_HIP;
-            }
-            if (b != ~0ull) ecc_units = b / cs.gcd;
+// 2b. the key-width proof from the real diameter, where the family is
+//     likely dense, the graph is not complete (complete graphs have the
+//     longest-edge bound) and (V-1) * max edge would not allow f16 keys;
+//     then the key proofs of the closure families
+srt_status prove_key_widths(Create &c) {
+    srt_plan *p = c.p;
+    const CsrStats &cs = c.cs;
+    open_create_timing(p);
+    // priced as if the proof gave 2-byte keys (it decides whether to run it)
+    const bool sym = cs.sym_a == cs.sym_b;
+    const bool dense_likely = c.want == SRT_ALGO_FW ||
+                              (c.want == SRT_ALGO_AUTO && srt::price_fw(p->Vp, c.n, p->V, srt::KEY_U16, true, sym) <
+                                                              srt::price_sparse(c.n, c.n_in, p->V, true));
+    // sparse plans need it too: the frontier sweeps keep u16 latencies
+    // when every finite distance is below 0xFFFF units (srt_frontier.hip)
+    const unsigned __int128 edge_bound = srt::proved_bound(cs, p->V, ~0ull);  // (V-1) * max edge
+    const bool sparse_u16 = !dense_likely && edge_bound >= 0xffff;
+    if (!cs.complete && (dense_likely || sparse_u16) && edge_bound >= 1024 && !c.knobs.fw_no_ecc) {
+        uint64_t b = ~0ull;
+        uint32_t sweeps = 0;
+        srt_err e2{};
+        if (srt::fw_ecc_bound(p, 512, &b, &sweeps, &e2) != SRT_OK) {
+            if (c.err) *c.err = e2;
+            return SRT_ERR_HIP;
         }
+        if (b != ~0ull) c.ecc_units = b / cs.gcd;
     }
-    (void)ecc_sweeps;
-    tr.mark("create: eccentricity sweeps");
-
-    // 3. kernel family: AUTO takes the cheaper representable one at the
-    //    measured rates (price_fw, price_sparse)
-    std::string why_fw, why_sssp;
-    bool f16 = false;
-    const bool fw_ok = choose_key_params(cs, p->V, ecc_units, &p->kp, &p->key_type, &f16, &why_fw);
+    c.tr.mark("create: eccentricity sweeps");
+    c.fw_ok = srt::choose_key_params(cs, p->V, c.ecc_units, c.knobs.fw_key, &p->kp, &p->key_type, &c.f16, &c.why_fw);
     // no parallel edges: the FW init can store edge keys instead of atomic-min'ing them
     p->fw_unique_edges = cs.unique;
-    const uint64_t n_in = g->n_adj - cs.selfloops;
-    const bool sssp_ok = sssp_params(cs, p->V, &why_sssp);
+    c.sssp_ok = srt::sssp_params(cs, p->V, &c.why_sssp);
     p->sssp_g = cs.gcd;
-    const uint32_t want = opts ? opts->algo : (uint32_t)SRT_ALGO_AUTO;
-    if (want > SRT_ALGO_LEVEL) return fail(SRT_ERR_INVALID, "unknown srt_opts.algo");
-    // 3a. the level solve (srt_loss.hip level_solve_kernel): asked for, or
-    //     AUTO on a graph whose row fits LDS.  The probe proves B, a bound
-    //     on every in-use shortest path over the edges <= min(31, max edge)
-    //     units; the solve applies when one was found (B <= 31).
-    uint64_t lvl_bound = ~0ull, lvl_visits = 0;
-    std::string why_lvl =
-        "the level solve needs V <= 18400 and every shortest path <= 63 latency units (or 63 buckets as wide "
-        "as the shortest edge)";
-    {
-        const uint64_t maxu = cs.maxlat / cs.gcd;
-        const bool fits = p->V >= 2 && p->V <= srt::LEVEL_V_MAX && n >= 1;
-        const char *kl = std::getenv("SRT_LEVEL");  // knob: 0 keeps AUTO off the level solve (A/B, tests)
-        const bool try_lvl = fits && maxu >= 1 &&
-                             (want == SRT_ALGO_LEVEL || (want == SRT_ALGO_AUTO && !(kl && std::atoi(kl) == 0)));
-        if (try_lvl) {
-            p->kp.g = cs.gcd;
-            p->lvl_q = 0;
-            p->lvl_maxu = maxu;
-            srt_err e2{};
-            auto probe_fail = [&]() {
-                srt_plan_destroy(p);
-                if (err) *err = e2;
-                return e2.code ? (srt_status)e2.code : SRT_ERR_HIP;
-            };
-            // complete graphs in identity rows whose pairs mirror exactly (the
-            // latencies here, over every pair; the losses too when they are on
-            // the device, else the one-call build checks the losses it
-            // gathers): one class CSR, the in-rows being the out-rows
-            const char *ks = std::getenv("SRT_LVL_SYM");  // knob: 0 = always build the in-rows (A/B, tests)
-            if (cs.complete && !(ks && std::atoi(ks) == 0)) {
-                bool sym = false;
-                if (dev_timed([&] { return srt::level_sym_check(p, maxu, !defer_loss, &sym, &e2); }) != SRT_OK)
-                    return probe_fail();
-                p->lvl_sym_lat = p->lvl_sym = sym;
-            }
-            // levels of one unit
-            auto probe = [&](uint64_t wmax, uint32_t wc) {
-                return dev_timed([&] { return srt::level_probe(p, wmax, wc, &lvl_bound, &lvl_visits, &e2); });
-            };
-            // 15 classes first (r06: C1-C3 prove B <= 14 there, and the probe CSR
-            // of the edges <= 15 units is half the one at 31), then 31, then 63
-            // (each also admits longer paths of short edges: bounds up to wc)
-            if (probe(std::min<uint64_t>(15, maxu), 15) != SRT_OK) return probe_fail();
-            if (lvl_bound == ~0ull && probe(std::min<uint64_t>(31, maxu), 31) != SRT_OK) return probe_fail();
-            if (lvl_bound == ~0ull && probe(std::min<uint64_t>(63, maxu), 63) != SRT_OK) return probe_fail();
-            // no bound within 63 units: the quantized solve, buckets of q <= the
-            // shortest edge (C3ns: g = 1 ns, edges >= 1 ms), when the shortest
-            // paths stay under 64 such buckets
-            const char *kq = std::getenv("SRT_LEVEL_Q");  // knob: 0 = integer levels only (A/B, tests)
-            if (lvl_bound == ~0ull && !(kq && std::atoi(kq) == 0)) {
-                uint64_t mn_ns = ~0ull;
-                if (dev_timed([&] { return srt::level_min_edge(p, &mn_ns, &e2); }) != SRT_OK) return probe_fail();
-                const uint64_t mu = mn_ns == ~0ull ? 0 : mn_ns / cs.gcd;
-                const uint32_t vb = srt::level_vbits(p->V);
-                // an entry keeps the remainder w - c q (< q) in 34 - vb bits;
-                // latencies up to 64 q stay below 2^31
-                const uint64_t q = std::min<uint64_t>(std::min<uint64_t>(mu, 1ull << (34 - vb)), 1ull << 25);
-                if (q >= 2) {
-                    uint32_t rb = 0;
-                    while ((1ull << rb) < q) ++rb;
-                    p->lvl_q = (uint32_t)q;
-                    p->lvl_rb = rb;
-                    p->lvl_vb = vb;
-                    if (probe(std::min<uint64_t>(maxu, 32 * q - 1), 31) != SRT_OK) return probe_fail();
-                    if (lvl_bound == ~0ull && probe(std::min<uint64_t>(maxu, 64 * q - 1), 63) != SRT_OK)
-                        return probe_fail();
-                    if (lvl_bound == ~0ull) p->lvl_q = 0;
-                }
-            }
-            // the probe's lists were sized for it; the run builds its own
-            p->t_edges = 0;
+    if (c.want > SRT_ALGO_LEVEL) return refuse(c.err, SRT_ERR_INVALID, "unknown srt_opts.algo");
+    return SRT_OK;
+}
+
+// the level probes of probe_level; their error goes to e2
+srt_status run_level_probes(Create &c, uint64_t maxu, srt_err *e2) {
+    srt_plan *p = c.p;
+    const CsrStats &cs = c.cs;
+    p->kp.g = cs.gcd;
+    p->lvl_q = 0;
+    p->lvl_maxu = maxu;
+    // complete graphs in identity rows whose pairs mirror exactly (the
+    // latencies here, over every pair; the losses too when they are on
+    // the device, else the one-call build checks the losses it
+    // gathers): one class CSR, the in-rows being the out-rows
+    if (cs.complete && !(c.knobs.lvl_sym.set && c.knobs.lvl_sym.v == 0)) {
+        bool sym = false;
+        ST_TRY(srt::level_sym_check(p, maxu, !c.defer_loss, &sym, e2));
+        p->lvl_sym_lat = p->lvl_sym = sym;
+    }
+    // levels of one unit
+    auto probe = [&](uint64_t wmax, uint32_t wc) {
+        return srt::level_probe(p, wmax, wc, &c.lvl_bound, &c.lvl_visits, e2);
+    };
+    // 15 classes first (r06: C1-C3 prove B <= 14 there, and the probe CSR
+    // of the edges <= 15 units is half the one at 31), then 31, then 63
+    // (each also admits longer paths of short edges: bounds up to wc)
+    ST_TRY(probe(std::min<uint64_t>(15, maxu), 15));
+    if (c.lvl_bound == ~0ull) ST_TRY(probe(std::min<uint64_t>(31, maxu), 31));
+    if (c.lvl_bound == ~0ull) ST_TRY(probe(std::min<uint64_t>(63, maxu), 63));
+    // no bound within 63 units: the quantized solve, buckets of q <= the
+    // shortest edge (C3ns: g = 1 ns, edges >= 1 ms), when the shortest
+    // paths stay under 64 such buckets
+    if (c.lvl_bound == ~0ull && !(c.knobs.level_q.set && c.knobs.level_q.v == 0)) {
+        uint64_t mn_ns = ~0ull;
+        ST_TRY(srt::level_min_edge(p, &mn_ns, e2));
+        const uint32_t vb = srt::level_vbits(p->V);
+        const srt::LevelQuantum lq = srt::level_quantum(mn_ns == ~0ull ? 0 : mn_ns / cs.gcd, vb);
+        if (lq.q >= 2) {
+            p->lvl_q = (uint32_t)lq.q;
+            p->lvl_rb = lq.rb;
+            p->lvl_vb = vb;
+            ST_TRY(probe(std::min<uint64_t>(maxu, 32 * lq.q - 1), 31));
+            if (c.lvl_bound == ~0ull) ST_TRY(probe(std::min<uint64_t>(maxu, 64 * lq.q - 1), 63));
+            if (c.lvl_bound == ~0ull) p->lvl_q = 0;
         }
     }
-    const bool lvl_ok = lvl_bound != ~0ull;
-    tr.mark("create: level probe");
-    int algo = -1;
-    std::string auto_note;
-    if (want == SRT_ALGO_FW) {
-        if (fw_ok) algo = SRT_ALGO_FW;
-    } else if (want == SRT_ALGO_SSSP) {
-        if (sssp_ok) algo = SRT_ALGO_SSSP;
-    } else if (want == SRT_ALGO_LEVEL) {
-        if (lvl_ok) algo = SRT_ALGO_LEVEL;
-    } else {
-        const uint64_t maxu = cs.maxlat / cs.gcd;
-        const unsigned __int128 lb = ecc_units != ~0ull ? (unsigned __int128)ecc_units
-                                                        : (unsigned __int128)(p->V ? p->V - 1 : 0) * maxu;
-        const double t_fw = fw_ok ? price_fw(p->Vp, n, p->V, p->key_type, f16, cs.sym_a == cs.sym_b) : 1e300;
-        const double t_sssp = sssp_ok ? price_sparse(n, n_in, p->V, lb < 0xffff) : 1e300;
-        const double t_lvl = lvl_ok ? price_level(n, p->V, lvl_visits) : 1e300;
-        char pr[128];
-        std::snprintf(pr, sizeof pr, " auto-price=fw:%.3gms,sparse:%.3gms,level:%.3gms", t_fw < 1e299 ? t_fw * 1e3 : -1.0,
-                      t_sssp < 1e299 ? t_sssp * 1e3 : -1.0, t_lvl < 1e299 ? t_lvl * 1e3 : -1.0);
-        auto_note = pr;
-        if (fw_ok || sssp_ok || lvl_ok)
-            algo = t_lvl <= std::min(t_fw, t_sssp) ? SRT_ALGO_LEVEL : t_sssp < t_fw ? SRT_ALGO_SSSP : SRT_ALGO_FW;
+    // the probe's lists were sized for it; the run builds its own
+    p->t_edges = 0;
+    return SRT_OK;
+}
+
+// 3a. the level solve (srt_loss.hip level_solve_kernel): asked for, or
+//     AUTO on a graph whose row fits LDS.  The probe proves B, a bound
+//     on every in-use shortest path over the edges <= min(31, max edge)
+//     units; the solve applies when one was found (B <= 31).
+srt_status probe_level(Create &c) {
+    srt_plan *p = c.p;
+    const uint64_t maxu = srt::max_units(c.cs);
+    const bool fits = p->V >= 2 && p->V <= srt::LEVEL_V_MAX && c.n >= 1;
+    const bool try_lvl = fits && maxu >= 1 &&
+                         (c.want == SRT_ALGO_LEVEL ||
+                          (c.want == SRT_ALGO_AUTO && !(c.knobs.level.set && c.knobs.level.v == 0)));
+    srt_err e2{};
+    if (try_lvl && run_level_probes(c, maxu, &e2) != SRT_OK) {
+        if (c.err) *c.err = e2;
+        return e2.code ? (srt_status)e2.code : SRT_ERR_HIP;
     }
-    if (algo < 0) {
-        const std::string why = want == SRT_ALGO_SSSP ? why_sssp
-                                : want == SRT_ALGO_FW ? why_fw
-                                : want == SRT_ALGO_LEVEL ? why_lvl
-                                                         : why_fw + "; " + why_sssp;
-        return fail(SRT_ERR_UNSUPPORTED, ("no exact path key for this graph: " + why).c_str());
+    c.tr.mark("create: level probe");
+    return SRT_OK;
+}
+
+// 3. kernel family: AUTO takes the cheaper representable one at the
+//    measured rates (price_fw, price_sparse, price_level)
+srt_status choose_family(Create &c) {
+    srt_plan *p = c.p;
+    const CsrStats &cs = c.cs;
+    const uint32_t n = c.n;
+    const bool lvl_ok = c.lvl_bound != ~0ull;
+    const srt::FamilyPick pick = srt::pick_family(
+        c.want, c.fw_ok, c.sssp_ok, lvl_ok, srt::price_fw(p->Vp, n, p->V, p->key_type, c.f16, cs.sym_a == cs.sym_b),
+        srt::price_sparse(n, c.n_in, p->V, srt::proved_bound(cs, p->V, c.ecc_units) < 0xffff),
+        srt::price_level(n, p->V, c.lvl_visits));
+    c.auto_note = pick.note;
+    if (pick.algo < 0) {
+        const std::string why_lvl =
+            "the level solve needs V <= 18400 and every shortest path <= 63 latency units (or 63 buckets as wide "
+            "as the shortest edge)";
+        const std::string why = c.want == SRT_ALGO_SSSP ? c.why_sssp
+                                : c.want == SRT_ALGO_FW ? c.why_fw
+                                : c.want == SRT_ALGO_LEVEL ? why_lvl
+                                                           : c.why_fw + "; " + c.why_sssp;
+        return refuse(c.err, SRT_ERR_UNSUPPORTED, ("no exact path key for this graph: " + why).c_str());
     }
-    p->algo = algo;
-    if (algo == SRT_ALGO_LEVEL) {
+    p->algo = pick.algo;
+    if (p->algo == SRT_ALGO_LEVEL) {
         // levels are exact integers <= B in units of g: 2-byte download records
         // (quantized: B < 32 << sh < 2^31, 4-byte ones)
         p->kp.g = cs.gcd;
-        p->kp.lmax = lvl_bound;
+        p->kp.lmax = c.lvl_bound;
         p->kp.lat32 = true;
         p->key_type = p->lvl_q ? srt::KEY_U32 : srt::KEY_U16;
-        f16 = false;
-
+        c.f16 = false;
+        p->desc = srt::describe_level(p->kp.g, p->lvl_q, p->kp.lmax, p->V, n, c.lvl_visits, p->lvl_sym,
+                                      p->d_lat16 != nullptr);
     } else {
         p->lvl_q = 0;
         p->lvl_sym = p->lvl_sym_lat = false;
@@ -1198,320 +970,213 @@ srt_status plan_create_impl(const srt_csr *g, const uint32_t *nodes, uint32_t n,
     }
     // SSSP plans read their in-edges (with loss) from the host-built list, never
     // d_loss: drop the deferred upload so run_tail does not copy it
-    if (algo == SRT_ALGO_SSSP) {
+    if (p->algo == SRT_ALGO_SSSP) {
         p->h_loss_defer = nullptr;
-        if (defer_loss && srt::first_bad_loss(g) != ~0ull)  // no device check on this path
-            return fail(SRT_ERR_INVALID, "Edge 'packet_loss' is not in the range [0,1]");
+        if (c.defer_loss && srt::first_bad_loss(c.g) != ~0ull)  // no device check on this path
+            return refuse(c.err, SRT_ERR_INVALID, "Edge 'packet_loss' is not in the range [0,1]");
     }
     p->row0 = 0;
     p->row1 = n;
     p->rows_alloc = n;
-    char d[200];
-    if (algo == SRT_ALGO_LEVEL) {
-        if (p->lvl_q)
-            std::snprintf(d, sizeof d, "level:u32 g=%llu q=%u lmax=%llu(probe) V=%u n=%u visits=%llu loss=in-solve%s",
-                          (unsigned long long)p->kp.g, p->lvl_q, (unsigned long long)p->kp.lmax, p->V, n,
-                          (unsigned long long)lvl_visits, p->lvl_sym ? (p->d_lat16 ? " rows=sym lat16" : " rows=sym") : "");
-        else
-            std::snprintf(d, sizeof d, "level:u16 g=%llu lmax=%llu(probe) V=%u n=%u visits=%llu loss=in-solve%s",
-                          (unsigned long long)p->kp.g, (unsigned long long)p->kp.lmax, p->V, n,
-                          (unsigned long long)lvl_visits, p->lvl_sym ? (p->d_lat16 ? " rows=sym lat16" : " rows=sym") : "");
-    } else if (algo == SRT_ALGO_FW) {
-        p->fw_f16 = f16 && p->fw_glds;
-        if (const char *e = std::getenv("SRT_FW_P1")) p->fw_p1 = std::atoi(e);
-        if (const char *e = std::getenv("SRT_FW_EMULATE_RANKS")) p->emulate_ranks = (uint32_t)std::atoi(e);
-        if (p->emulate_ranks > 1) {
-            // emulated rank 0 owns the first max(1, blocks / N) block-rows (fw_rounds_t)
-            const uint32_t nblk = p->Vp / srt::FW_B;
-            const uint32_t rows_per = std::max<uint32_t>(1, nblk / p->emulate_ranks) * srt::FW_B;
-            if (srt_status st = build_loss_rows(p, (int)p->emulate_ranks, rows_per, err); st != SRT_OK) {
-                srt_plan_destroy(p);
-                return st;
-            }
-        }
-        if (const char *e = std::getenv("SRT_FW_BAND")) p->fw_band = e[0] == '1';
-        std::snprintf(d, sizeof d, "fw:%s B=%d g=%llu lmax=%llu%s V=%u n=%u stage=%s band=%d loss=tight-dag%s",
-                      p->fw_f16                     ? "f16key"
-                      : p->key_type == srt::KEY_U16 ? "u16key"
-                      : p->key_type == srt::KEY_U32 ? "u32key"
-                      : p->key_type == srt::KEY_F64 ? "f64key"
-                                                    : "u64key",
-                      srt::FW_B, (unsigned long long)p->kp.g, (unsigned long long)p->kp.lmax,
-                      cs.complete ? "(complete)" : ecc_units != ~0ull && ecc_units == p->kp.lmax ? "(ecc)" : "(V-1)",
-                      p->V, n,
-                      p->fw_glds ? "glds" : "reg", (int)p->fw_band, p->kp.lat32 ? "/u32" : "/u64");
-    } else {
-        // R words of 64 sources per lane (one wave walks a vertex's in-edges
-        // once for 64*R sources), and as many groups in flight as ~256 MB of
-        // path state allows (Infinity Cache sized), never more than the rows need
-        const uint32_t words = std::max<uint32_t>(1, (n + 63) / 64);
-        // Many groups in flight amortise each sweep's launch and latency chain
-        // and the convergence tail (C4, measured: 192 MB of path state 3.0 s,
-        // 1.6 GB 1.73 s, 6.4 GB 1.53 s, 12.8 GB 1.49 s), capped at 1/8 of the
-        // free HBM.
-        uint64_t budget_mb = 6400;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b)
-            budget_mb = std::max<uint64_t>(64, std::min<uint64_t>(budget_mb, (free_b >> 20) / 8));
-        const uint32_t R = words >= 4 ? 4 : words >= 2 ? 2 : 1;
-        const uint64_t per_group = (uint64_t)p->V * 64 * 8 * R;
-        uint64_t G = std::max<uint64_t>(1, (budget_mb << 20) / std::max<uint64_t>(per_group, 1));
-        G = std::min<uint64_t>(G, (words + R - 1) / R);
-        G = std::min<uint64_t>(G, 256);
-        p->sssp_r = R;
-        p->sssp_nb = (uint32_t)(G * R);
-        p->n_in_edges = n_in;
-        d[0] = '\0';  // named once the bucket width is known (below)
-    }
-    p->desc = d;
-    tr.mark("create: key/algo choice");
+    return SRT_OK;
+}
 
-    // 4. the family's buffers; self-loop values
-    srt_status st;
-    hipError_t e;
-#define PLAN_TRY(x)                \
-    do {                           \
-        st = (x);                  \
-        if (st != SRT_OK) {        \
-            srt_plan_destroy(p);   \
-            return st;             \
-        }                          \
-    } while (0)
-    if (algo == SRT_ALGO_FW)
-        PLAN_TRY(dmalloc(reinterpret_cast<uint8_t **>(&p->d_D), (size_t)p->Vp * p->Vp * srt::key_bytes(p->key_type),
-                         err));
-    PLAN_TRY(dmalloc(&p->d_out_lat, (size_t)n * n, err));
-    PLAN_TRY(dmalloc(&p->d_out_loss, (size_t)n * n, err));
-    if (algo == SRT_ALGO_SSSP) {
-        std::vector<uint64_t> in_ptr;
-        std::vector<srt::InEdge> in_edge;
-        build_in_edges(g, p->sssp_g, n_in, &in_ptr, &in_edge);
-        // latency-first frontier sweeps (srt_frontier.hip) when every finite
-        // distance fits u16 units: the proved bound (eccentricity, or (V-1) *
-        // max edge) below 0xFFFF.  Knob SRT_SSSP_KEY=64 keeps the packed-key
-        // sweep (A/B, tests).
-        {
-            const uint64_t maxu = cs.maxlat / cs.gcd;
-            const unsigned __int128 lb = ecc_units != ~0ull ? (unsigned __int128)ecc_units
-                                                            : (unsigned __int128)(p->V ? p->V - 1 : 0) * maxu;
-            const char *kk = std::getenv("SRT_SSSP_KEY");
-            p->sssp_frontier = lb < 0xffff && !(kk && std::atoi(kk) == 64);
-        }
-        PLAN_TRY(dmalloc(&p->d_in_ptr, in_ptr.size(), err));
-        PLAN_TRY(dmalloc(&p->d_in_edge, in_edge.size(), err));
-        // source order of the sweep's words (knob SRT_SSSP_ORDER=0: table order)
-        {
-            const char *ko = std::getenv("SRT_SSSP_ORDER");
-            const int om = ko ? std::atoi(ko) : 1;
-            // 1: launches in breadth-first order, rows within a launch in
-            // shortest-latency-tree level order (frontier sweeps); 2: breadth-first
-            // only; 3: tree level order only (A/B)
-            if (om == 1 || om == 2) p->h_bfs_rank = hop_rank(g);
-            if (om == 3) p->h_bfs_rank = spt_rank(g);
-            if (om == 1 && p->sssp_frontier) p->h_spt_rank = spt_rank(g);  // read by frontier sweeps only
-        }
-        if (!p->sssp_frontier) {
-            PLAN_TRY(dmalloc(&p->d_sD, (size_t)p->sssp_nb * p->V * 64, err));
-            PLAN_TRY(dmalloc(&p->d_smask, (size_t)2 * p->sssp_nb * p->V, err));
-            PLAN_TRY(dmalloc(&p->d_sflag, (size_t)12 * p->sssp_nb, err));  // flags + delta-stepping ring
-            PLAN_TRY(dmalloc(&p->d_spend, (size_t)p->sssp_nb * p->V, err));
-        }
-        {
-            // delta-stepping bucket width = SRT_SSSP_DELTA x the mean in-edge
-            // latency (units of g); default 0 = ungated sweeps, the faster on
-            // C4 (100k BA, one GPU: ungated 1.60 s, factor 0.25 / 1.0 1.68 s --
-            // fewer relaxations but not fewer gathered lines)
-            double f = 0.0;
-            if (const char *ev = std::getenv("SRT_SSSP_DELTA")) f = std::atof(ev);
-            double sum = 0.0;
-            for (const srt::InEdge &ie : in_edge) sum += ie.w;
-            const double mean = in_edge.empty() ? 0.0 : sum / (double)in_edge.size();
-            p->sssp_delta = f > 0.0 ? (uint32_t)std::max(1.0, std::min(mean * f, 1e9)) : 0u;
-            // sweep bound: V + 2 Bellman-Ford sweeps once the threshold passes
-            // the longest simple path, plus the sweeps it takes to get there
-            uint64_t wmax = 0;
-            for (const srt::InEdge &ie : in_edge) wmax = std::max<uint64_t>(wmax, ie.w);
-            p->sssp_tmax = (uint64_t)p->V + 4;
-            if (p->sssp_delta) p->sssp_tmax += (uint64_t)p->V * wmax / p->sssp_delta + 2;
-        }
-        char dd[256];
-        std::snprintf(dd, sizeof dd, "sssp:lat32|f32 g=%llu V=%u n=%u E_in=%llu R=%u groups=%u delta=%u order=%s",
-                      (unsigned long long)p->sssp_g, p->V, p->n, (unsigned long long)p->n_in_edges, p->sssp_r,
-                      p->sssp_nb / p->sssp_r, p->sssp_delta, p->h_bfs_rank.empty() ? "table" : "bfs");
-        p->desc = dd;
-        if (const char *ev = std::getenv("SRT_SSSP_ACT")) {
-            const int k = std::atoi(ev);
-            p->sssp_act_on = k != 0;
-            p->sssp_act_from = k > 1 ? (uint32_t)k : 0u;
-        }
-        if (p->sssp_frontier) {
-            // blocks in flight: as many as half the free HBM holds (C4: ~0.7 GB a
-            // block, capped at 64 = 32k sources), never more than the rows need;
-            // knob SRT_SSSP_FR_NB (measurement)
-            const uint64_t bb = srt::frontier_block_bytes(p->V, n_in);
-            size_t free_b = 0, total_b = 0;
-            uint64_t nb = 64;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b)
-                nb = std::min<uint64_t>(nb, std::max<uint64_t>(1, (free_b / 2) / std::max<uint64_t>(bb, 1)));
-            // launches of equal size (C4: 196 blocks as 4 x 49, not 64+64+64+4 --
-            // a small last launch pays a full run of sweeps: 0.70 -> 0.68 s)
-            const uint64_t blocks_all = std::max<uint32_t>(1, (n + 511) / 512);
-            nb = (blocks_all + (blocks_all + nb - 1) / nb - 1) / ((blocks_all + nb - 1) / nb);
-            if (const char *ev = std::getenv("SRT_SSSP_FR_NB")) nb = std::max<uint64_t>(1, std::atoll(ev));
-            nb = std::min<uint64_t>(nb, blocks_all);
-            p->fr_nb = (uint32_t)nb;
-            int cus = 256;
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device);
-            p->fr_grid = (uint32_t)std::max(1, cus) * 8;
-            if (const char *ev = std::getenv("SRT_SSSP_FR_GRID")) p->fr_grid = (uint32_t)std::max(1, std::atoi(ev));
-            // undirected (latency-symmetric) graphs: L(s, v) = L(v, s), so every
-            // launch starts from the exact columns of the earlier launches' rows
-            // (srt_frontier.hip fr_sym_copy_kernel) -- which needs the latencies
-            // of all rows resident: n * V * 2 B (C4: 20 GB), if a quarter of the
-            // free HBM holds them.  Knob SRT_SSSP_SYM=0 (A/B, tests).
-            const uint64_t all_blocks = std::max<uint32_t>(1, (n + 511) / 512);
-            const char *ks = std::getenv("SRT_SSSP_SYM");
-            p->fr_symg = latency_symmetric(g, in_ptr, in_edge, cs.gcd);
-            p->fr_sym = !(ks && std::atoi(ks) == 0) && all_blocks > nb &&
-                        all_blocks * p->V * 1024ull <= (uint64_t)free_b / 4 && p->fr_symg;
-            // a smaller first launch: the only one whose latency phase starts
-            // from the sources alone (C4, 4 launches: 49+49+49+49 blocks 0.488 s,
-            // 12+61+61+62 0.463, 20+... 0.465, 28+... 0.463); ~1/12 of the
-            // blocks, the rest keep the launch count, so their buffers grow to
-            // hold them.  Knob SRT_FR_FIRST = blocks (0: equal launches; A/B).
-            p->fr_first = 0;
-            if (p->fr_sym) {
-                const char *ev = std::getenv("SRT_FR_FIRST");
-                const uint64_t f = ev ? std::atoll(ev) : all_blocks / 12, k = (all_blocks + nb - 1) / nb;
-                if (f > 0 && f < nb && k >= 2) {
-                    const uint64_t rest = (all_blocks - f + k - 2) / (k - 1);
-                    if (rest <= 64 && rest * bb <= free_b / 2) {
-                        nb = std::max(nb, rest);
-                        p->fr_first = (uint32_t)f;
-                        p->fr_nb = (uint32_t)nb;
-                    }
-                }
-            }
-            p->fr_lblocks = p->fr_sym ? (uint32_t)all_blocks : (uint32_t)nb;
-            PLAN_TRY(dmalloc(&p->d_fl, (size_t)p->fr_lblocks * p->V * 512, err));
-            PLAN_TRY(dmalloc(&p->d_fp, (size_t)nb * p->V * 512, err));
-            PLAN_TRY(dmalloc(&p->d_ftight, (size_t)nb * std::max<uint64_t>(n_in, 1) * 64, err));
-            PLAN_TRY(dmalloc(&p->d_fce, (size_t)nb * std::max<uint64_t>(n_in, 1), err));
-            PLAN_TRY(dmalloc(&p->d_fcnt, (size_t)nb * p->V, err));
-            PLAN_TRY(dmalloc(&p->d_fctl, 8, err));
-            PLAN_TRY(dmalloc(reinterpret_cast<uint8_t **>(&p->d_fchg), (size_t)nb * p->V * srt::frontier_chg_bytes(), err));
-            PLAN_TRY(dmalloc(&p->d_fact, (size_t)nb * p->V, err));
-            PLAN_TRY(dmalloc(&p->d_fsb, (size_t)2 * nb * p->V * 64, err));
-            PLAN_TRY(dmalloc(&p->d_ffin, (size_t)nb * p->V, err));
-            PLAN_TRY(dmalloc(&p->d_fimp, 1, err));
-            if ((e = hipMemsetAsync(p->d_fchg, 0, (size_t)nb * p->V * srt::frontier_chg_bytes(), p->stream)) != hipSuccess ||
-                (e = hipMemsetAsync(p->d_fact, 0, (size_t)nb * p->V * 4, p->stream)) != hipSuccess ||
-                (e = hipMemsetAsync(p->d_fimp, 0, 4, p->stream)) != hipSuccess ||
-                (e = hipHostMalloc((void **)&p->h_fimp, 4, 0)) != hipSuccess) {
-                srt_plan_destroy(p);
-                return hip_fail(err, e, "sparse frontier buffers");
-            }
-            p->fr_t = 1;
-            char df[160];
-            std::snprintf(df, sizeof df,
-                          "sssp:frontier u16|f32 g=%llu lmax=%llu%s V=%u n=%u E_in=%llu blocks=%u first=%u order=%s seed=%s",
-                          (unsigned long long)p->sssp_g, (unsigned long long)(ecc_units != ~0ull ? ecc_units : 0),
-                          ecc_units != ~0ull ? "(ecc)" : "(V-1)", p->V, p->n, (unsigned long long)p->n_in_edges,
-                          p->fr_nb, p->fr_first,
-                          p->h_bfs_rank.empty() ? "table" : p->h_spt_rank.empty() ? "bfs" : "bfs+tree",
-                          p->fr_sym ? "sym" : "none");
-            p->desc = df;
-        }
-        if (p->sssp_act_on && !p->sssp_frontier)
-            PLAN_TRY(dmalloc(&p->d_sact, (size_t)3 * (p->sssp_nb / p->sssp_r) * p->V, err));
-        if ((e = hipHostMalloc((void **)&p->h_sflag, (size_t)p->sssp_nb * sizeof(uint32_t), 0)) != hipSuccess) {
-            srt_plan_destroy(p);
-            return hip_fail(err, e, "hipHostMalloc");
-        }
-        if (p->sssp_frontier) {
-            // Hub-spreading vertex order for the frontier sweeps: a wave works
-            // through a 64-vertex chunk item by item, so a chunk of hubs (BA
-            // graphs number them first: C4's vertices 0..63 have ~1000
-            // in-edges each) would keep one wave busy for the whole sweep
-            // (measured: C4 1.71 s -> 1.07 s with the hubs dealt out).  The
-            // cpb highest in-degree vertices go to slot 0 of the cpb chunks,
-            // one each; every other vertex keeps its relative order (BA graphs'
-            // id locality: neighbours of similar age gather similar rows).
-            const uint32_t V = p->V, cpb = (V + 63) / 64;
-            std::vector<uint32_t> order(V), pi(V, ~0u);
-            for (uint32_t v = 0; v < V; ++v) order[v] = v;
-            std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-                return in_ptr[a + 1] - in_ptr[a] > in_ptr[b + 1] - in_ptr[b];
-            });
-            // (measured, C4: no hubs dealt 1.30 s, the top 64 0.95 s, one per chunk 0.80 s)
-            const uint32_t H = V >= 64 * cpb ? cpb : (V > cpb ? cpb - 1 : 0);  // chunks with a full slot 0
-            std::vector<uint8_t> hub(V, 0);
-            for (uint32_t h = 0; h < H; ++h) {
-                pi[order[h]] = h * 64;
-                hub[order[h]] = 1;
-            }
-            for (uint32_t v = 0, pos = 0; v < V; ++v) {
-                if (hub[v]) continue;
-                while (pos % 64 == 0 && pos / 64 < H) ++pos;  // slot 0 of a hub chunk
-                pi[v] = pos++;
-            }
-            std::vector<uint64_t> ip(V + 1, 0), op(V + 1, 0);
-            for (uint32_t v = 0; v < V; ++v) {
-                ip[pi[v] + 1] = in_ptr[v + 1] - in_ptr[v];
-                uint64_t d = 0;
-                for (uint64_t k = g->row_ptr[v]; k < g->row_ptr[v + 1]; ++k) d += g->col[k] != v;
-                op[pi[v] + 1] = d;
-            }
-            for (uint32_t v = 0; v < V; ++v) {
-                ip[v + 1] += ip[v];
-                op[v + 1] += op[v];
-            }
-            std::vector<srt::InEdge> ie(in_edge.size());
-            std::vector<uint32_t> oc(std::max<uint64_t>(op[V], 1));
-            for (uint32_t v = 0; v < V; ++v) {
-                uint64_t o = ip[pi[v]];
-                for (uint64_t k = in_ptr[v]; k < in_ptr[v + 1]; ++k, ++o) {
-                    ie[o] = in_edge[k];
-                    ie[o].u = pi[in_edge[k].u];
-                }
-                o = op[pi[v]];
-                for (uint64_t k = g->row_ptr[v]; k < g->row_ptr[v + 1]; ++k)
-                    if (g->col[k] != v) oc[o++] = pi[g->col[k]];
-            }
-            in_ptr.swap(ip);
-            in_edge.swap(ie);
-            p->h_fnodes.resize(n);
-            for (uint32_t i = 0; i < n; ++i) p->h_fnodes[i] = pi[nodes[i]];
-            PLAN_TRY(dmalloc(&p->d_fnodes, std::max<uint32_t>(n, 1), err));
-            PLAN_TRY(dmalloc(&p->d_frow_ptr, op.size(), err));
-            PLAN_TRY(dmalloc(&p->d_fcol, oc.size(), err));
-            if ((e = hipMemcpy(p->d_fnodes, p->h_fnodes.data(), (size_t)n * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = hipMemcpy(p->d_frow_ptr, op.data(), op.size() * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = hipMemcpy(p->d_fcol, oc.data(), oc.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) {
-                srt_plan_destroy(p);
-                return hip_fail(err, e, "upload frontier graph");
-            }
-        }
-        if ((e = hipMemcpy(p->d_in_ptr, in_ptr.data(), in_ptr.size() * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy(p->d_in_edge, in_edge.data(), in_edge.size() * sizeof(srt::InEdge),
-                           hipMemcpyHostToDevice)) != hipSuccess) {
-            srt_plan_destroy(p);
-            return hip_fail(err, e, "upload in-edges");
-        }
+// the free device memory the sparse families size themselves by; 0: unknown
+uint64_t free_device_bytes() {
+    size_t free_b = 0, total_b = 0;
+    return hipMemGetInfo(&free_b, &total_b) == hipSuccess ? (uint64_t)free_b : 0;
+}
+
+// Floyd-Warshall plans: the schedule's knobs, the emulated ranks' loss rows
+srt_status setup_fw(Create &c) {
+    srt_plan *p = c.p;
+    const CreateKnobs &k = c.knobs;
+    p->fw_f16 = c.f16 && p->fw_glds;
+    if (k.fw_p1.set) p->fw_p1 = k.fw_p1.v;
+    if (k.fw_emulate_ranks.set) p->emulate_ranks = (uint32_t)k.fw_emulate_ranks.v;
+    if (p->emulate_ranks > 1) {
+        // emulated rank 0 owns the first max(1, blocks / N) block-rows (fw_rounds_t)
+        const uint32_t nblk = p->Vp / srt::FW_B;
+        const uint32_t rows_per = std::max<uint32_t>(1, nblk / p->emulate_ranks) * srt::FW_B;
+        ST_TRY(build_loss_rows(p, (int)p->emulate_ranks, rows_per, c.err));
     }
-#undef PLAN_TRY
-    p->h_sl_lat = std::move(sl_lat);
-    p->h_sl_loss = std::move(sl_loss);
-    if ((n && (e = hipMemcpyAsync(p->d_sl_lat, p->h_sl_lat.data(), (size_t)n * 8, hipMemcpyHostToDevice,
-                                  p->stream)) != hipSuccess) ||
-        (n && (e = hipMemcpyAsync(p->d_sl_loss, p->h_sl_loss.data(), (size_t)n * 4, hipMemcpyHostToDevice,
-                                  p->stream)) != hipSuccess) ||
-        (e = hipStreamSynchronize(p->stream)) != hipSuccess) {
-        srt_plan_destroy(p);
-        return hip_fail(err, e, "upload");
+    if (k.fw_band.set) p->fw_band = k.fw_band.v;
+    p->desc = srt::describe_fw(p->fw_f16, p->key_type, p->kp, c.cs.complete, c.ecc_units, p->V, c.n, p->fw_glds,
+                               p->fw_band);
+    return SRT_OK;
+}
+
+// sparse plans: the packed sweep's words in flight (named once the bucket
+// width is known, setup_sparse)
+void size_sparse_groups(Create &c) {
+    srt_plan *p = c.p;
+    const srt::SsspGroups sg = srt::sssp_groups(c.n, p->V, free_device_bytes());
+    p->sssp_r = sg.R;
+    p->sssp_nb = sg.nb;
+    p->n_in_edges = c.n_in;
+}
+
+// 4. the family's buffers: the closure's keys, the table
+srt_status alloc_table(Create &c) {
+    srt_plan *p = c.p;
+    if (p->algo == SRT_ALGO_FW)
+        ST_TRY(dmalloc(reinterpret_cast<uint8_t **>(&p->d_D), (size_t)p->Vp * p->Vp * srt::key_bytes(p->key_type),
+                       c.err));
+    ST_TRY(dmalloc(&p->d_out_lat, (size_t)c.n * c.n, c.err));
+    ST_TRY(dmalloc(&p->d_out_loss, (size_t)c.n * c.n, c.err));
+    return SRT_OK;
+}
+
+// the sparse graph on the host: in-edge CSR (self-loops dropped)
+struct SparseGraph {
+    std::vector<uint64_t> in_ptr;
+    std::vector<srt::InEdge> in_edge;
+};
+
+// sparse plans, both sweeps: the in-edges, the sweep (frontier or packed keys),
+// the source order, the bucket width and the sweep bound
+srt_status setup_sparse_common(Create &c, SparseGraph &s) {
+    srt_plan *p = c.p;
+    const CreateKnobs &k = c.knobs;
+    srt::build_in_edges(c.g, p->sssp_g, c.n_in, &s.in_ptr, &s.in_edge);
+    // latency-first frontier sweeps (srt_frontier.hip) when every finite
+    // distance fits u16 units: the proved bound (eccentricity, or (V-1) *
+    // max edge) below 0xFFFF.  Knob SRT_SSSP_KEY=64 keeps the packed-key
+    // sweep (A/B, tests).
+    p->sssp_frontier =
+        srt::proved_bound(c.cs, p->V, c.ecc_units) < 0xffff && !(k.sssp_key.set && k.sssp_key.v == 64);
+    ST_TRY(dmalloc(&p->d_in_ptr, s.in_ptr.size(), c.err));
+    ST_TRY(dmalloc(&p->d_in_edge, s.in_edge.size(), c.err));
+    // source order of the sweep's words (knob SRT_SSSP_ORDER=0: table order).
+    // 1: launches in breadth-first order, rows within a launch in
+    // shortest-latency-tree level order (frontier sweeps); 2: breadth-first
+    // only; 3: tree level order only (A/B)
+    const int om = k.sssp_order.set ? k.sssp_order.v : 1;
+    if (om == 1 || om == 2) p->h_bfs_rank = srt::hop_rank(c.g);
+    if (om == 3) p->h_bfs_rank = srt::spt_rank(c.g);
+    if (om == 1 && p->sssp_frontier) p->h_spt_rank = srt::spt_rank(c.g);  // read by frontier sweeps only
+    // delta-stepping bucket width = SRT_SSSP_DELTA x the mean in-edge
+    // latency (units of g); default 0 = ungated sweeps, the faster on
+    // C4 (100k BA, one GPU: ungated 1.60 s, factor 0.25 / 1.0 1.68 s --
+    // fewer relaxations but not fewer gathered lines)
+    const double f = k.sssp_delta.set ? k.sssp_delta.v : 0.0;
+    double sum = 0.0;
+    for (const srt::InEdge &ie : s.in_edge) sum += ie.w;
+    const double mean = s.in_edge.empty() ? 0.0 : sum / (double)s.in_edge.size();
+    p->sssp_delta = f > 0.0 ? (uint32_t)std::max(1.0, std::min(mean * f, 1e9)) : 0u;
+    // sweep bound: V + 2 Bellman-Ford sweeps once the threshold passes
+    // the longest simple path, plus the sweeps it takes to get there
+    uint64_t wmax = 0;
+    for (const srt::InEdge &ie : s.in_edge) wmax = std::max<uint64_t>(wmax, ie.w);
+    p->sssp_tmax = (uint64_t)p->V + 4;
+    if (p->sssp_delta) p->sssp_tmax += (uint64_t)p->V * wmax / p->sssp_delta + 2;
+    if (k.sssp_act.set) {
+        p->sssp_act_on = k.sssp_act.v != 0;
+        p->sssp_act_from = k.sssp_act.v > 1 ? (uint32_t)k.sssp_act.v : 0u;
     }
-    tr.mark("create: upload");
-    p->desc += auto_note;
+    return SRT_OK;
+}
+
+// the packed-key sweep's buffers
+srt_status setup_packed_sweep(Create &c) {
+    srt_plan *p = c.p;
+    ST_TRY(dmalloc(&p->d_sD, (size_t)p->sssp_nb * p->V * 64, c.err));
+    ST_TRY(dmalloc(&p->d_smask, (size_t)2 * p->sssp_nb * p->V, c.err));
+    ST_TRY(dmalloc(&p->d_sflag, (size_t)12 * p->sssp_nb, c.err));  // flags + delta-stepping ring
+    ST_TRY(dmalloc(&p->d_spend, (size_t)p->sssp_nb * p->V, c.err));
+    p->desc = srt::describe_sssp(p->sssp_g, p->V, p->n, p->n_in_edges, p->sssp_r, p->sssp_nb / p->sssp_r,
+                                 p->sssp_delta, p->h_bfs_rank.empty());
+    if (p->sssp_act_on) ST_TRY(dmalloc(&p->d_sact, (size_t)3 * (p->sssp_nb / p->sssp_r) * p->V, c.err));
+    return SRT_OK;
+}
+
+// the frontier sweeps' launch geometry (srt_choose.cpp frontier_geometry) and buffers
+srt_status setup_frontier(Create &c, const SparseGraph &s) {
+    srt_plan *p = c.p;
+    srt_err *err = c.err;
+    const uint64_t n_in = c.n_in, free_b = free_device_bytes();
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device);
+    p->fr_grid = (uint32_t)std::max(1, cus) * 8;
+    if (c.knobs.sssp_fr_grid.set) p->fr_grid = (uint32_t)std::max(1, c.knobs.sssp_fr_grid.v);
+    p->fr_symg = srt::latency_symmetric(c.g, s.in_ptr, s.in_edge, c.cs.gcd);
+    const srt::FrontierGeometry fg =
+        srt::frontier_geometry(c.n, p->V, srt::frontier_block_bytes(p->V, n_in), free_b, p->fr_symg, c.knobs);
+    p->fr_nb = fg.nb;
+    p->fr_first = fg.first;
+    p->fr_sym = fg.sym;
+    p->fr_lblocks = fg.lblocks;
+    const size_t nb = fg.nb;
+    ST_TRY(dmalloc(&p->d_fl, (size_t)p->fr_lblocks * p->V * 512, err));
+    ST_TRY(dmalloc(&p->d_fp, nb * p->V * 512, err));
+    ST_TRY(dmalloc(&p->d_ftight, nb * std::max<uint64_t>(n_in, 1) * 64, err));
+    ST_TRY(dmalloc(&p->d_fce, nb * std::max<uint64_t>(n_in, 1), err));
+    ST_TRY(dmalloc(&p->d_fcnt, nb * p->V, err));
+    ST_TRY(dmalloc(&p->d_fctl, 8, err));
+    ST_TRY(dmalloc(reinterpret_cast<uint8_t **>(&p->d_fchg), nb * p->V * srt::frontier_chg_bytes(), err));
+    ST_TRY(dmalloc(&p->d_fact, nb * p->V, err));
+    ST_TRY(dmalloc(&p->d_fsb, (size_t)2 * nb * p->V * 64, err));
+    ST_TRY(dmalloc(&p->d_ffin, nb * p->V, err));
+    ST_TRY(dmalloc(&p->d_fimp, 1, err));
+    HIP_TRY(hipMemsetAsync(p->d_fchg, 0, nb * p->V * srt::frontier_chg_bytes(), p->stream), "sparse frontier buffers");
+    HIP_TRY(hipMemsetAsync(p->d_fact, 0, nb * p->V * 4, p->stream), "sparse frontier buffers");
+    HIP_TRY(hipMemsetAsync(p->d_fimp, 0, 4, p->stream), "sparse frontier buffers");
+    HIP_TRY(hipHostMalloc((void **)&p->h_fimp, 4, 0), "sparse frontier buffers");
+    p->fr_t = 1;
+    p->desc = srt::describe_frontier(p->sssp_g, c.ecc_units, p->V, p->n, p->n_in_edges, p->fr_nb, p->fr_first,
+                                     p->h_bfs_rank.empty(), !p->h_spt_rank.empty(), p->fr_sym);
+    return SRT_OK;
+}
+
+// the frontier's vertex order (srt_choose.cpp frontier_vertex_order): s
+// permuted, the in-use nodes and the out-CSR in that order uploaded
+srt_status upload_frontier_order(Create &c, SparseGraph &s) {
+    srt_plan *p = c.p;
+    srt_err *err = c.err;
+    srt::FrontierOrder fo = srt::frontier_vertex_order(c.g, c.nodes, c.n, &s.in_ptr, &s.in_edge);
+    p->h_fnodes = std::move(fo.fnodes);
+    ST_TRY(dmalloc(&p->d_fnodes, std::max<uint32_t>(c.n, 1), err));
+    ST_TRY(dmalloc(&p->d_frow_ptr, fo.row_ptr.size(), err));
+    ST_TRY(dmalloc(&p->d_fcol, fo.col.size(), err));
+    HIP_TRY(hipMemcpy(p->d_fnodes, p->h_fnodes.data(), (size_t)c.n * 4, hipMemcpyHostToDevice), "upload frontier graph");
+    HIP_TRY(hipMemcpy(p->d_frow_ptr, fo.row_ptr.data(), fo.row_ptr.size() * 8, hipMemcpyHostToDevice),
+            "upload frontier graph");
+    HIP_TRY(hipMemcpy(p->d_fcol, fo.col.data(), fo.col.size() * 4, hipMemcpyHostToDevice), "upload frontier graph");
+    return SRT_OK;
+}
+
+// sparse plans: the sweep's buffers and the in-edges' upload
+srt_status setup_sparse(Create &c) {
+    srt_plan *p = c.p;
+    srt_err *err = c.err;
+    SparseGraph s;
+    ST_TRY(setup_sparse_common(c, s));
+    ST_TRY(p->sssp_frontier ? setup_frontier(c, s) : setup_packed_sweep(c));
+    HIP_TRY(hipHostMalloc((void **)&p->h_sflag, (size_t)p->sssp_nb * sizeof(uint32_t), 0), "hipHostMalloc");
+    if (p->sssp_frontier) ST_TRY(upload_frontier_order(c, s));
+    HIP_TRY(hipMemcpy(p->d_in_ptr, s.in_ptr.data(), s.in_ptr.size() * 8, hipMemcpyHostToDevice), "upload in-edges");
+    HIP_TRY(hipMemcpy(p->d_in_edge, s.in_edge.data(), s.in_edge.size() * sizeof(srt::InEdge), hipMemcpyHostToDevice),
+            "upload in-edges");
+    return SRT_OK;
+}
+
+// the self-loop values' upload, the end of the stream's work and of the
+// timed span: srt_timing.create_device_ms
+srt_status finish_create(Create &c) {
+    srt_plan *p = c.p;
+    srt_err *err = c.err;
+    const uint32_t n = c.n;
+    p->h_sl_lat = std::move(c.sl_lat);
+    p->h_sl_loss = std::move(c.sl_loss);
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(p->d_sl_lat, p->h_sl_lat.data(), (size_t)n * 8, hipMemcpyHostToDevice, p->stream),
+                "upload");
+        HIP_TRY(hipMemcpyAsync(p->d_sl_loss, p->h_sl_loss.data(), (size_t)n * 4, hipMemcpyHostToDevice, p->stream),
+                "upload");
+    }
+    HIP_TRY(hipStreamSynchronize(p->stream), "upload");
+    c.tr.mark("create: upload");
+    p->desc += c.auto_note;
     p->in_create = false;
     p->create_device_ms = 0.0;
     for (size_t i = 0; i + 1 < p->cspan.size(); i += 2) {
@@ -1520,7 +1185,36 @@ srt_status plan_create_impl(const srt_csr *g, const uint32_t *nodes, uint32_t n,
     }
     for (hipEvent_t e : p->cspan) (void)hipEventDestroy(e);
     p->cspan.clear();
-    *plan_out = p;
+    return SRT_OK;
+}
+
+// Plan creation as its stages; a failing stage has set *err, and the plan
+// built so far is destroyed on the way out.
+srt_status plan_create_impl(const srt_csr *g, const uint32_t *nodes, uint32_t n, const srt_opts *opts,
+                            srt_plan **plan_out, srt_err *err, bool defer_loss) {
+    clear_err(err);
+    srt::init_wait();  // a pending srt_init_async finishes before any device work
+    // plans an earlier one-call build queued for teardown free their HBM
+    // before this plan sizes itself (hipMemGetInfo) or allocates anything
+    reap_drain();
+    Create c{g, nodes, n, opts, err, defer_loss};
+    read_create_knobs(c.knobs);
+    c.want = opts ? opts->algo : (uint32_t)SRT_ALGO_AUTO;
+    ST_TRY(check_arguments(g, nodes, n, plan_out, err));
+    std::unique_ptr<srt_plan, PlanDelete> plan(new_plan(g, nodes, n));
+    if (!plan) return refuse(err, SRT_ERR_OOM, "out of host memory");
+    srt_plan *p = c.p = plan.get();
+    ST_TRY(reference_errors(c, scan_beside_device_setup(c)));
+    ST_TRY(prove_key_widths(c));
+    ST_TRY(probe_level(c));
+    ST_TRY(choose_family(c));
+    if (p->algo == SRT_ALGO_FW) ST_TRY(setup_fw(c));
+    if (p->algo == SRT_ALGO_SSSP) size_sparse_groups(c);
+    c.tr.mark("create: key/algo choice");
+    ST_TRY(alloc_table(c));
+    if (p->algo == SRT_ALGO_SSSP) ST_TRY(setup_sparse(c));
+    ST_TRY(finish_create(c));
+    *plan_out = plan.release();
     return SRT_OK;
 }
 

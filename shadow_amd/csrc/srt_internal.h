@@ -27,7 +27,7 @@ namespace srt {
 // latencies, each <= lmax) stays below KEY16_INF (packed: v_pk_add_u16 +
 // v_pk_min_u16 relax two keys per instruction pair -- the fastest), else u32
 // below KEY32_INF (v_add_u32 + v_min3_u32), else f64 below 2^53, else u64
-// below KEY_INF; the host proves it (choose_key_params in srt_api.cpp).
+// below KEY_INF; the host proves it (choose_key_params in srt_choose.cpp).
 constexpr uint64_t KEY_INF = 1ull << 62;  // INF + INF < 2^64: no wrap in the closure
 constexpr uint32_t KEY32_INF = 0x7fffffffu;  // u32 keys: INF + INF < 2^32
 constexpr uint16_t KEY16_INF = 0x7fff;       // u16 keys: INF + INF < 2^16
@@ -187,7 +187,6 @@ struct srt_plan {
     std::vector<hipEvent_t> ev_fold;      // emulation: D holds the closure (first run done)
     uint64_t emu_tight = 0, emu_maxw = 0;  // emulation: tight edges / max latency of the closure
     std::string desc;
-    bool identity_nodes = false;
     bool ident_rows = false;  // the adjacency is V identity rows (host scan, CsrStats::ident)
     bool ident_nodes = false;  // the in-use nodes are 0 .. V-1 in order (nodes[j] = j, n = V)
     double create_device_ms = 0.0;  // device work of srt_plan_create (probes, symmetry / bound checks)

@@ -1,7 +1,7 @@
 """The GPU-free host code of libsrt -- GML ingest, the CSR scan, the .xz
 decoder, IpAssignment and its resolver, RoutingInfo's concurrent path() and
-counters -- and the oracle, built for the CPU under AddressSanitizer and
-UndefinedBehaviorSanitizer (tests/asan/Makefile: every -fsanitize= after
+counters, plan creation's host decisions (srt_choose.cpp) -- and the oracle,
+built for the CPU under AddressSanitizer and UndefinedBehaviorSanitizer (tests/asan/Makefile: every -fsanitize= after
 -Xarch_host) and driven by tests/asan/host_check.cpp with generated, truncated
 and corrupted inputs; the threaded parts also under ThreadSanitizer.  Any
 sanitizer report fails the run."""
