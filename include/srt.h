@@ -244,7 +244,18 @@ typedef struct {
     uint64_t t_ns; /* emulated time at send */
 } srt_pkt;
 
-enum { SRT_PDS_NONE = 0, SRT_PDS_INET_SENT = 1u << 8, SRT_PDS_INET_DROPPED = 1u << 9 };
+/* PacketDeliveryStatusFlags (src/main/routing/packet.minimal.h:24-36): the send
+ * decision's two and the inbound router stage's five */
+enum {
+    SRT_PDS_NONE = 0,
+    SRT_PDS_INET_SENT = 1u << 8,
+    SRT_PDS_INET_DROPPED = 1u << 9,
+    SRT_PDS_ROUTER_ENQUEUED = 1u << 10,
+    SRT_PDS_ROUTER_DEQUEUED = 1u << 11,
+    SRT_PDS_ROUTER_DROPPED = 1u << 12,
+    SRT_PDS_RELAY_CACHED = 1u << 21,
+    SRT_PDS_RELAY_FORWARDED = 1u << 22
+};
 
 typedef struct {
     uint64_t round_end_ns;
@@ -295,6 +306,117 @@ srt_status srt_packet_events(srt_plan *plan, const uint32_t *d_host_pkt_ptr, uin
  * redoes that call's sort exactly (its arrays must still be valid) and
  * returns SRT_OK; else SRT_OK. */
 srt_status srt_packet_events_status(srt_plan *plan, srt_err *err);
+
+/* --------------------------------------------------- inbound router stage */
+/* What the destination host does with the packet events srt_packet_events
+ * ordered, batched over hosts: each packet event pushes its packet into the
+ * host's upstream Router, a CoDel queue (network/router/mod.rs:57-61,
+ * router/codel_queue.rs: TARGET 10 ms, INTERVAL 100 ms, no length limit), and
+ * the host's relay_inet_in drains that queue into the network interface under
+ * a token bucket sized from bandwidth_down (network/relay/mod.rs:200-287,
+ * relay/token_bucket.rs: 1 ms refills of max(1, bytes_per_second / 1000),
+ * capacity one refill + CONFIG_MTU; host.rs:303-305, 855-858, 977-979).  At
+ * one host, events run in time order and at equal times every packet event
+ * runs before the relay's forward task (core/work/event.rs:102-110).  The
+ * stage decides which packets the router drops (ROUTER_DROPPED) and when every
+ * other packet reaches the interface (RELAY_FORWARDED at forward_ns); it is
+ * exact, state included, and a pure function of the arrival order, the deliver
+ * times, the packet sizes and each host's download bandwidth.
+ * OUT OF SCOPE: the CPU-delay model that reschedules events (host.rs:820-848),
+ * the loopback relay and the outbound relay (is_local is always false here),
+ * and anything the interface does after it receives the packet.
+ * ABI: additive to version 4; detect the stage by its symbols. */
+typedef struct srt_inbound srt_inbound;
+
+/* a packet of an EARLIER call that left the stage in this one */
+typedef struct {
+    uint64_t seq;        /* its call's seq_base + its batch index */
+    uint64_t forward_ns; /* UINT64_MAX unless forwarded */
+    uint32_t status;     /* SRT_PDS_* */
+    uint32_t dst_host;
+} srt_inbound_late;
+
+/* one host's state (tests, checkpoints, event-id accounting) */
+typedef struct {
+    uint64_t balance;             /* TokenBucket */
+    uint64_t last_refill_ns;
+    uint64_t interval_end_ns;     /* CoDelQueue; UINT64_MAX = None */
+    uint64_t drop_next_ns;        /* UINT64_MAX = None */
+    uint64_t current_drop_count;
+    uint64_t previous_drop_count;
+    uint64_t queue_len;           /* packets in the CoDel queue */
+    uint64_t bytes_stored;
+    uint64_t task_ns;             /* pending forward task; UINT64_MAX = relay Idle */
+    uint64_t tasks_scheduled;     /* forward tasks scheduled so far: each took one of the
+                                     host's event ids (Host::get_new_event_id) */
+    uint32_t mode;                /* 0 Store, 1 Drop */
+    uint32_t cached;              /* 1: the relay holds a cached next_packet */
+    uint32_t overflow;            /* 1: this host's ring overflowed, its results are invalid */
+    uint32_t reserved0;
+} srt_inbound_host_state;
+
+/* srt_inbound_status flags */
+#define SRT_INBOUND_RING_OVERFLOW 1u   /* a host held more unresolved packets than queue_cap */
+#define SRT_INBOUND_LATE_OVERFLOW 2u   /* more late records than late_cap (the rest are lost) */
+#define SRT_INBOUND_TIME_REGRESSION 4u /* an arrival earlier than the previous call's until_ns */
+#define SRT_INBOUND_OVERSIZE 8u        /* a packet larger than its host's token bucket can hold: the
+                                          reference would reschedule it for ever; here its forward
+                                          task is tried once a call (task_ns moved to until_ns) */
+#define SRT_INBOUND_AFTER_UNTIL 16u    /* an arrival at or after until_ns: not taken (status 0) */
+
+/* State for n_hosts destination hosts on the plan's device and stream, or,
+ * with plan == NULL, a host-only instance: every array argument of the other
+ * calls is then a HOST pointer and the calls complete before they return.
+ * Both forms run the same per-host step.  bw_down_bytes_per_s: HOST pointer,
+ * each host's requested bandwidth_down in bits / 8.  queue_cap: packets a
+ * host may hold unresolved (queued) across calls; the rings take
+ * n_hosts * queue_cap * 24 bytes.  Buckets start full, last refill at 0.
+ * Destroy the instance before its plan (it runs on the plan's stream). */
+srt_status srt_inbound_create(srt_plan *plan, uint32_t n_hosts, const uint64_t *bw_down_bytes_per_s,
+                              uint32_t queue_cap, srt_inbound **out, srt_err *err);
+/* One scheduling window.  d_order / d_dst_ptr: srt_packet_events' outputs
+ * (dst_ptr has n_hosts + 1 entries, n_hosts as at create); d_deliver: the
+ * deliver times; d_total_size: every packet's payload plus headers; all
+ * indexed by batch index, n_pkts of them (order[] holds dst_ptr[n_hosts]).
+ * The batch's arrivals must lie in the window [previous call's until_ns,
+ * until_ns): every one of them is pushed at its deliver time and every forward
+ * task with a time < until_ns runs.  An earlier arrival is flagged
+ * (TIME_REGRESSION); an arrival at or after until_ns belongs to a later window
+ * and is NOT taken -- its status stays 0, it is not pending, and the call is
+ * flagged (AFTER_UNTIL) so that the caller feeds it again with that window.
+ * Before bootstrap_end_ns the bucket is not touched (worker.rs:489-491).
+ * Outputs, per batch packet: d_status (0 for a packet that is not in
+ * order[] or was not taken; ENQUEUED | DROPPED; ENQUEUED | DEQUEUED | FORWARDED, plus CACHED
+ * if the relay ever held it back; still in the stage at until_ns: ENQUEUED,
+ * or ENQUEUED | DEQUEUED | CACHED for the relay's cached packet) and
+ * d_forward_ns (UINT64_MAX unless forwarded).  A packet still in the stage
+ * stays there under the sequence number *seq_base + batch index (seq_base,
+ * host pointer, may be NULL: the running count of all earlier calls' n_pkts).
+ * Packets of earlier calls that leave in this one are appended to d_late
+ * (late_cap records, any order) and counted in *d_late_count (written by the
+ * call; beyond late_cap: SRT_INBOUND_LATE_OVERFLOW).
+ * Asynchronous on the plan's stream, like srt_packet_events. */
+srt_status srt_inbound_run(srt_inbound *ib, const uint32_t *d_order, const uint32_t *d_dst_ptr,
+                           const uint64_t *d_deliver, const uint32_t *d_total_size, uint64_t n_pkts,
+                           uint64_t until_ns, uint64_t bootstrap_end_ns, uint32_t *d_status,
+                           uint64_t *d_forward_ns, srt_inbound_late *d_late, uint32_t late_cap,
+                           uint32_t *d_late_count, uint64_t *seq_base, srt_err *err);
+/* Synchronises the stream.  *flags (may be NULL): the SRT_INBOUND_* conditions
+ * met since the last status call (then cleared); *n_pending (may be NULL):
+ * packets still in the stage.  SRT_ERR_INVALID when a flag is set (a ring
+ * overflow never writes out of bounds: the host is marked in its state and
+ * only its results are invalid), else SRT_OK. */
+srt_status srt_inbound_status(srt_inbound *ib, uint32_t *flags, uint64_t *n_pending, srt_err *err);
+/* Synchronises and copies every host's state to out[n_hosts] (HOST pointer). */
+srt_status srt_inbound_state(srt_inbound *ib, srt_inbound_host_state *out, srt_err *err);
+/* apply_control_law's increment, round(1e8 / sqrt(count)) in f64 with count 0
+ * as 1 (codel_queue.rs:287-300), for counts[0 .. n) (HOST pointers), evaluated
+ * where the instance runs (on the device for a plan's instance).  use_table
+ * != 0: as the stage evaluates it (a host-built table below 1024, f64 above);
+ * 0: the f64 path for every count. */
+srt_status srt_inbound_control_law(srt_inbound *ib, const uint64_t *counts, uint64_t n, int use_table,
+                                   uint64_t *increments, srt_err *err);
+void srt_inbound_destroy(srt_inbound *ib);
 
 /* ---------------------------------------------------- IP assignment (a10) */
 /* IpAssignment<u32> (src/main/network/graph/mod.rs:352-420): IPv4 address ->

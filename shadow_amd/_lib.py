@@ -24,6 +24,11 @@ SRT_ERR_COMM = 8
 SRT_ALGO_AUTO, SRT_ALGO_FW, SRT_ALGO_SSSP, SRT_ALGO_LEVEL = 0, 1, 2, 3
 SRT_OPT_SAME_DEVICE = 1  # srt_opts.flags: every n_gpus rank on `device` (tests)
 PDS_NONE, PDS_INET_SENT, PDS_INET_DROPPED = 0, 1 << 8, 1 << 9
+PDS_ROUTER_ENQUEUED, PDS_ROUTER_DEQUEUED, PDS_ROUTER_DROPPED = 1 << 10, 1 << 11, 1 << 12
+PDS_RELAY_CACHED, PDS_RELAY_FORWARDED = 1 << 21, 1 << 22
+# srt_inbound_status flags
+INBOUND_RING_OVERFLOW, INBOUND_LATE_OVERFLOW, INBOUND_TIME_REGRESSION, INBOUND_OVERSIZE = 1, 2, 4, 8
+INBOUND_AFTER_UNTIL = 16
 
 
 class SrtErr(C.Structure):
@@ -61,6 +66,18 @@ class SrtTiming(C.Structure):
 
 class SrtRound(C.Structure):
     _fields_ = [("round_end_ns", C.c_uint64), ("bootstrap_end_ns", C.c_uint64), ("sim_end_ns", C.c_uint64)]
+
+
+class SrtInboundLate(C.Structure):
+    _fields_ = [("seq", C.c_uint64), ("forward_ns", C.c_uint64), ("status", C.c_uint32), ("dst_host", C.c_uint32)]
+
+
+class SrtInboundHostState(C.Structure):
+    _fields_ = [("balance", C.c_uint64), ("last_refill_ns", C.c_uint64), ("interval_end_ns", C.c_uint64),
+                ("drop_next_ns", C.c_uint64), ("current_drop_count", C.c_uint64),
+                ("previous_drop_count", C.c_uint64), ("queue_len", C.c_uint64), ("bytes_stored", C.c_uint64),
+                ("task_ns", C.c_uint64), ("tasks_scheduled", C.c_uint64), ("mode", C.c_uint32),
+                ("cached", C.c_uint32), ("overflow", C.c_uint32), ("reserved0", C.c_uint32)]
 
 
 class SrtError(RuntimeError):
@@ -113,6 +130,13 @@ SIGNATURES = {
     "srt_packet_events_status": (C.c_int, [_vp, _errp]),
     "srt_packet_events": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp,
                                     _vp, _errp]),
+    "srt_inbound_create": (C.c_int, [_vp, C.c_uint32, _u64p, C.c_uint32, C.POINTER(_vp), _errp]),
+    "srt_inbound_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp,
+                                  C.c_uint32, _vp, _u64p, _errp]),
+    "srt_inbound_status": (C.c_int, [_vp, _u32p, _u64p, _errp]),
+    "srt_inbound_state": (C.c_int, [_vp, C.POINTER(SrtInboundHostState), _errp]),
+    "srt_inbound_control_law": (C.c_int, [_vp, _u64p, C.c_uint64, C.c_int, _u64p, _errp]),
+    "srt_inbound_destroy": (None, [_vp]),
     "srt_routing_info_build": (C.c_int, [C.POINTER(SrtCsr), _u32p, C.c_uint32, C.c_int, C.POINTER(SrtOpts),
                                          C.POINTER(_vp), _errp]),
     "srt_routing_info_from_plan": (C.c_int, [_vp, C.POINTER(_vp), _errp]),

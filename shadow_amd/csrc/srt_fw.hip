@@ -3086,6 +3086,7 @@ hipError_t preload_sssp();
 hipError_t preload_packet();
 hipError_t preload_direct();
 hipError_t preload_events();
+hipError_t preload_inbound();
 hipError_t preload_kernels() {
     hipError_t e = preload_fw();
     if (e == hipSuccess) e = preload_loss();
@@ -3093,6 +3094,7 @@ hipError_t preload_kernels() {
     if (e == hipSuccess) e = preload_packet();
     if (e == hipSuccess) e = preload_direct();
     if (e == hipSuccess) e = preload_events();
+    if (e == hipSuccess) e = preload_inbound();
     return e;
 }
 

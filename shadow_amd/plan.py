@@ -105,6 +105,8 @@ class RoutingPlan:
         return self._h
 
     def close(self):
+        for r in list(getattr(self, "_routers", ())):  # InboundRouter objects bound to this plan
+            r.close()
         if self._h:
             _lib.lib().srt_plan_destroy(self._h)
             self._h = C.c_void_p()
@@ -196,3 +198,131 @@ class RoutingPlan:
         """srt_packet_status: synchronises; raises if a batch met an address without a row."""
         err = _lib.SrtErr()
         _lib.check(_lib.lib().srt_packet_status(self._h, C.byref(err)), err)
+
+
+INBOUND_STATE_DTYPE = np.dtype([(k, "<u8") for k in (
+    "balance", "last_refill_ns", "interval_end_ns", "drop_next_ns", "current_drop_count", "previous_drop_count",
+    "queue_len", "bytes_stored", "task_ns", "tasks_scheduled")] + [(k, "<u4") for k in (
+        "mode", "cached", "overflow", "reserved0")])
+INBOUND_LATE_DTYPE = np.dtype([("seq", "<u8"), ("forward_ns", "<u8"), ("status", "<u4"), ("dst_host", "<u4")])
+
+
+_live_routers = None  # device-bound InboundRouter objects, closed before the interpreter finalises
+
+
+def _close_live_routers():
+    for r in list(_live_routers or ()):
+        try:
+            r.close()
+        except Exception:
+            pass
+
+
+class InboundRouter:
+    """srt_inbound: every destination host's CoDel queue and download token
+    bucket (router/codel_queue.rs, relay/mod.rs, relay/token_bucket.rs) behind
+    the packet events, one call per scheduling window.
+
+    Bound to a RoutingPlan (arrays are torch CUDA tensors of its device, the
+    call is asynchronous on its stream; closing the plan closes its routers), or
+    host-only with plan=None (arrays are numpy arrays, the same per-host step
+    on the CPU)."""
+
+    def __init__(self, plan: Optional[RoutingPlan], bw_down_bytes_per_s, queue_cap: int):
+        self.plan = plan
+        bw = np.ascontiguousarray(bw_down_bytes_per_s, np.uint64)
+        self.n_hosts = len(bw)
+        self._h = C.c_void_p()
+        if plan is not None:  # the plan closes its routers before itself (they run on its stream)
+            import weakref
+
+            if not hasattr(plan, "_routers"):
+                plan._routers = weakref.WeakSet()
+            plan._routers.add(self)
+            # a router left open (a caller that raised) is closed while the HIP
+            # runtime is still up, not by a finaliser during interpreter shutdown
+            global _live_routers
+            if _live_routers is None:
+                import atexit
+
+                _live_routers = weakref.WeakSet()
+                atexit.register(_close_live_routers)
+            _live_routers.add(self)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_inbound_create(plan.handle if plan is not None else None, self.n_hosts,
+                                                 bw.ctypes.data_as(C.POINTER(C.c_uint64)), int(queue_cap),
+                                                 C.byref(self._h), C.byref(err)), err)
+
+    @staticmethod
+    def _ptr(a):
+        if a is None:
+            return None
+        return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+    def run(self, order, dst_ptr, deliver, total_size, until_ns: int, bootstrap_end_ns: int, status, forward_ns,
+            late=None, late_count=None) -> int:
+        """srt_inbound_run.  order int32/uint32 (srt_packet_events' output), dst_ptr
+        [n_hosts+1], deliver int64/uint64, total_size int32/uint32, outputs
+        status int32/uint32 and forward_ns int64/uint64, all [n_pkts]; late: a
+        uint8 buffer of 24-byte srt_inbound_late records (INBOUND_LATE_DTYPE)
+        with late_count a 1-element int32/uint32.  Returns the batch's sequence
+        base.  Device form: enqueue only (status() synchronises)."""
+        n_pkts = int(status.numel() if hasattr(status, "numel") else status.size)
+        late_cap = 0
+        if late is not None:
+            late_cap = int(late.numel() * late.element_size() if hasattr(late, "numel") else late.nbytes) // 24
+        cur = ps = None
+        if self.plan is not None:
+            import torch
+
+            ps = torch.cuda.ExternalStream(self.plan.stream_ptr(), device=status.device)
+            cur = torch.cuda.current_stream(status.device)
+            ps.wait_stream(cur)
+        base = C.c_uint64()
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_inbound_run(
+            self._h, self._ptr(order), self._ptr(dst_ptr), self._ptr(deliver), self._ptr(total_size), n_pkts,
+            int(until_ns), int(bootstrap_end_ns), self._ptr(status), self._ptr(forward_ns), self._ptr(late), late_cap,
+            self._ptr(late_count), C.byref(base), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)  # torch-side consumers see the outputs (device-side ordering)
+        return base.value
+
+    def status(self, check: bool = True):
+        """srt_inbound_status: synchronises; (flags, packets still pending).
+        check=True raises SrtError when a flag is set."""
+        flags, pending = C.c_uint32(), C.c_uint64()
+        err = _lib.SrtErr()
+        rc = _lib.lib().srt_inbound_status(self._h, C.byref(flags), C.byref(pending), C.byref(err))
+        if check or (rc != _lib.SRT_OK and not flags.value):
+            _lib.check(rc, err)
+        return flags.value, pending.value
+
+    def state(self) -> np.ndarray:
+        """Every host's state (INBOUND_STATE_DTYPE record array)."""
+        out = np.zeros(self.n_hosts, INBOUND_STATE_DTYPE)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_inbound_state(
+            self._h, out.ctypes.data_as(C.POINTER(_lib.SrtInboundHostState)), C.byref(err)), err)
+        return out
+
+    def control_law(self, counts, use_table: bool = True) -> np.ndarray:
+        """apply_control_law's increments for `counts`, evaluated where the stage runs."""
+        c = np.ascontiguousarray(counts, np.uint64)
+        out = np.zeros(len(c), np.uint64)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_inbound_control_law(
+            self._h, c.ctypes.data_as(C.POINTER(C.c_uint64)), len(c), int(use_table),
+            out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(err)), err)
+        return out
+
+    def close(self):
+        if self._h:
+            _lib.lib().srt_inbound_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
