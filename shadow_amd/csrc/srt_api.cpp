@@ -607,6 +607,9 @@ void read_create_knobs(CreateKnobs &k) {
     read("SRT_LEVEL", k.level, as_int);
     read("SRT_LVL_SYM", k.lvl_sym, as_int);
     read("SRT_LEVEL_Q", k.level_q, as_int);
+    read("SRT_LVL_NT", k.lvl_nt, as_int);
+    read("SRT_LVL_SP", k.lvl_sp, as_int);
+    read("SRT_LVL_DYN", k.lvl_dyn, as_int);
     read("SRT_FW_P1", k.fw_p1, as_int);
     read("SRT_FW_EMULATE_RANKS", k.fw_emulate_ranks, as_int);
     read("SRT_FW_BAND", k.fw_band, [](const char *e) { return e[0] == '1'; });
@@ -861,6 +864,10 @@ srt_status run_level_probes(Create &c, uint64_t maxu, srt_err *e2) {
     p->kp.g = cs.gcd;
     p->lvl_q = 0;
     p->lvl_maxu = maxu;
+    // the launch knobs of this plan's solves, the probes' among them
+    p->lvl_nt = !(c.knobs.lvl_nt.set && c.knobs.lvl_nt.v == 0);
+    p->lvl_sp = !(c.knobs.lvl_sp.set && c.knobs.lvl_sp.v == 0);
+    p->lvl_dyn = !(c.knobs.lvl_dyn.set && c.knobs.lvl_dyn.v == 0);
     // complete graphs in identity rows whose pairs mirror exactly (the
     // latencies here, over every pair; the losses too when they are on
     // the device, else the one-call build checks the losses it
@@ -902,7 +909,7 @@ srt_status run_level_probes(Create &c, uint64_t maxu, srt_err *e2) {
     return SRT_OK;
 }
 
-// 3a. the level solve (srt_loss.hip level_solve_kernel): asked for, or
+// 3a. the level solve (srt_level.hip level_solve_kernel): asked for, or
 //     AUTO on a graph whose row fits LDS.  The probe proves B, a bound
 //     on every in-use shortest path over the edges <= min(31, max edge)
 //     units; the solve applies when one was found (B <= 31).
@@ -1710,7 +1717,7 @@ srt_status srt_plan_bind_comm(srt_plan *p, srt_comm *comm, srt_err *err) {
         if (p->algo == SRT_ALGO_SSSP) return SRT_OK;
         if (p->algo == SRT_ALGO_LEVEL) {
             // rows dealt by node index ranges, solved into a 6-byte staging
-            // and all-gathered chunk by chunk (srt_loss.hip level_sharded)
+            // and all-gathered chunk by chunk (srt_level.hip level_sharded)
             if (srt_status st = build_loss_rows(p, comm->nranks, (p->V + W - 1) / W, err); st != SRT_OK) return st;
             return SRT_OK;
         }

@@ -29,6 +29,9 @@ struct CreateKnobs {
     Knob<int> level;              // SRT_LEVEL: 0 keeps AUTO off the level solve (A/B, tests)
     Knob<int> lvl_sym;            // SRT_LVL_SYM: 0 = always build the in-rows (A/B, tests)
     Knob<int> level_q;            // SRT_LEVEL_Q: 0 = integer levels only (A/B, tests)
+    Knob<int> lvl_nt;             // SRT_LVL_NT: 0 = the level solve's table rows by plain stores (A/B, tests)
+    Knob<int> lvl_sp;             // SRT_LVL_SP: 0 = its per-item walk, not the pipelined one (A/B, tests)
+    Knob<int> lvl_dyn;            // SRT_LVL_DYN: 0 = its rows dealt statically, not by a counter (A/B, tests)
     Knob<int> fw_p1;              // SRT_FW_P1: u16/f16 phase 1, 1 = two FW steps per barrier, 0 = one (A/B)
     Knob<int> fw_emulate_ranks;   // SRT_FW_EMULATE_RANKS: rank 0's share of an N-rank schedule (measurement only)
     Knob<bool> fw_band;           // SRT_FW_BAND=1: grouped launches in banded tile order

@@ -3082,6 +3082,7 @@ hipError_t preload_fw() {
 }
 
 hipError_t preload_loss();
+hipError_t preload_level();
 hipError_t preload_sssp();
 hipError_t preload_packet();
 hipError_t preload_direct();
@@ -3090,6 +3091,7 @@ hipError_t preload_inbound();
 hipError_t preload_kernels() {
     hipError_t e = preload_fw();
     if (e == hipSuccess) e = preload_loss();
+    if (e == hipSuccess) e = preload_level();
     if (e == hipSuccess) e = preload_sssp();
     if (e == hipSuccess) e = preload_packet();
     if (e == hipSuccess) e = preload_direct();

@@ -338,7 +338,7 @@ struct srt_plan {
     uint32_t t_q = 1;                // level width of the fold, units of g (1: exact levels; > 1: quantized)
     uint32_t t_cls = 16;             // class offsets per vertex of the level fold's CSRs (16 or 32)
     uint32_t *d_tcw = nullptr;       // quantized fold: each class entry's exact weight (out, then in), t_cap each
-    uint64_t lvl_cap = 0;            // level solve: class entries d_tpk / d_tpk2 hold (the probe's count)
+    uint64_t lvl_cap = 0;            // level solve (srt_level.hip): class entries d_tpk / d_tpk2 hold (the probe's count)
     bool lvl_sym_lat = false;        // level solve: identity rows, mirrored latencies (lvl_sym_tile_kernel)
     bool lvl_sym = false;            // ... and mirrored losses: the class in-rows are the out-rows
     uint16_t *d_lat16 = nullptr;     // symmetric level plans: the adjacency's latencies in units of g (< 0xffff), written by the symmetry check
@@ -356,6 +356,7 @@ struct srt_plan {
     uint32_t lvl_emu_ranks = 0;      // measurement (srt_plan_shard_rows + SRT_LVL_SHARD_EMU=1): rank row0's slice
     bool lvl_emu_built = false;      // ... every slice built once (the first run); later runs rebuild the own one
     unsigned long long *d_rowctr = nullptr;  // level solve: the rows dealt by a counter (LevelCtx::row_ctr)
+    bool lvl_nt = true, lvl_sp = true, lvl_dyn = true;  // its launch knobs, read at create (CreateKnobs): LevelCtx::nt_store, sp, row_ctr
     unsigned long long *d_lvisit = nullptr;  // level solve: class entries the last run walked
     uint32_t lvl_q = 0, lvl_rb = 0, lvl_vb = 0;  // quantized level solve: bucket width (units), entry field bits
     uint16_t *d_lmem = nullptr;              // its per-workgroup scratch (lmem_cap u16)
@@ -477,7 +478,7 @@ srt_status fw_gather_keys(srt_plan *p, srt_err *err);
 // table rows, the raw self-loop diagonal and (min latency, unreachable) into
 // d_stats
 srt_status fw_loss(srt_plan *p, unsigned long long *d_stats, srt_err *err);
-// level solve (srt_loss.hip, SRT_ALGO_LEVEL): the create-time bound on every
+// level solve (srt_level.hip, SRT_ALGO_LEVEL): the create-time bound on every
 // in-use shortest path over the edges <= wmax units (~0: none; visits: edges a
 // row walks), and the build of rows [row0, row1) into the table
 srt_status level_probe(srt_plan *p, uint64_t wmax, uint32_t wc, uint64_t *bound, uint64_t *visits, srt_err *err);
@@ -501,6 +502,8 @@ struct LevelCtx {
     uint16_t *lmem = nullptr;              // quantized solve: level_scratch_bytes of per-workgroup scratch
     bool idn = false;                      // nodes[j] = j, n = V, n % 4 == 0: the vectorised row output
     unsigned long long *row_ctr = nullptr; // level solve: {next row, workgroups done}, 0 between launches (nullable: rows dealt statically)
+    bool nt_store = true;                  // table rows by non-temporal stores
+    bool sp = true;                        // the pipelined class walk (false: the per-item walk)
 };
 LevelCtx level_ctx(srt_plan *p);
 // the class CSRs of a level plan at its bound (the run's first step)

@@ -1,4 +1,4 @@
-"""GPU parity of the level solve (SRT_ALGO_LEVEL, srt_loss.hip
+"""GPU parity of the level solve (SRT_ALGO_LEVEL, srt_level.hip
 level_solve_kernel): per-source bucket Dijkstra over the edges of at most B
 latency units, B the create-time probe's bound on every in-use shortest path.
 
@@ -251,6 +251,68 @@ def test_level_63_unit_levels():
         _check(p.fetch(), og, nodes)
     finally:
         p.close()
+
+
+_KNOBS = [None, "SRT_LVL_SP", "SRT_LVL_NT", "SRT_LVL_DYN"]
+
+
+def _graph_63_levels():
+    """test_level_63_unit_levels' graph."""
+    n = 300
+    src, dst, lat, loss = synth.random_graph(n, 8, p_edge=0.012, directed=False, lat_range_ns=(1, 9), loss_max=0.05)
+    lat = np.asarray(lat, np.uint64) * np.uint64(synth.MS)
+    g = NetworkGraph.from_edges(n, src, dst, lat, loss)
+    return g, np.arange(n, dtype=np.uint32), O.Graph(False, np.arange(n), src, dst, lat, loss)
+
+
+def _run_with_knob(monkeypatch, knob, g, nodes, og, lmax_lo, lmax_hi, kind="level:u16 "):
+    """One create + run with `knob`=0 (None: the defaults), read at the create;
+    the class table is the intended one (lmax within [lmax_lo, lmax_hi])."""
+    if knob:
+        monkeypatch.setenv(knob, "0")
+    try:
+        p = RoutingPlan(g, nodes, algo=_lib.SRT_ALGO_LEVEL, device=0)
+    finally:
+        if knob:
+            monkeypatch.delenv(knob)
+    try:
+        d = p.describe()
+        lmax = int(d.split(" lmax=")[1].split("(")[0])
+        assert d.startswith(kind) and lmax_lo <= lmax <= lmax_hi, d
+        _check(p.run().fetch(), og, nodes)
+    finally:
+        p.close()
+
+
+@pytest.mark.parametrize("shape", ["general16", "identity32", "classes64"])
+def test_level_launch_knobs(monkeypatch, shape):
+    """The launch knobs are per plan (read at the create), so one process runs
+    the kernels the defaults never pick: the per-item walk (SRT_LVL_SP=0),
+    plain table stores (SRT_LVL_NT=0) and statically dealt rows
+    (SRT_LVL_DYN=0), each bit-exact against the oracle beside the default.
+    general16: V = 301 (no multiple of 4: the scalar tails of the row's init
+    and compaction), 200 permuted in-use nodes (the general row writer), 16
+    class offsets.  identity32: every node in node order (the vectorised row
+    writer), 32 class offsets.  classes64: 64 class offsets, per-item walk."""
+    if shape == "general16":
+        g, nodes, og = _random(301, 50, False, (1, 9), 0.08, 200)
+        lo, hi, knobs = 1, 15, _KNOBS
+    elif shape == "identity32":
+        g, _, og = _random(300, 62, False, (1, 20), 0.05)
+        nodes = np.arange(300, dtype=np.uint32)
+        lo, hi, knobs = 16, 31, _KNOBS
+    else:
+        g, nodes, og = _graph_63_levels()
+        lo, hi, knobs = 32, 63, ["SRT_LVL_SP"]
+    for knob in knobs:
+        _run_with_knob(monkeypatch, knob, g, nodes, og, lo, hi)
+
+
+def test_level_quantized_launch_knobs(monkeypatch):
+    """The quantized solve's plain-store kernel (SRT_LVL_NT=0) on the smallest
+    graph of test_level_quantized_matches_oracle."""
+    g, nodes, og = _random_ns(60, 1, False, 0.3, (1, 9), None)
+    _run_with_knob(monkeypatch, "SRT_LVL_NT", g, nodes, og, 0, 1 << 62, kind="level:u32 ")
 
 
 def test_level_quantized_equals_fw_dense():
