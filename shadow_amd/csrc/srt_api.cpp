@@ -610,6 +610,8 @@ void read_create_knobs(CreateKnobs &k) {
     read("SRT_LVL_NT", k.lvl_nt, as_int);
     read("SRT_LVL_SP", k.lvl_sp, as_int);
     read("SRT_LVL_DYN", k.lvl_dyn, as_int);
+    read("SRT_LVL_PACK", k.lvl_pack, as_int);
+    read("SRT_LVL_SPREAD", k.lvl_spread, as_int);
     read("SRT_FW_P1", k.fw_p1, as_int);
     read("SRT_FW_EMULATE_RANKS", k.fw_emulate_ranks, as_int);
     read("SRT_FW_BAND", k.fw_band, [](const char *e) { return e[0] == '1'; });
@@ -868,6 +870,7 @@ srt_status run_level_probes(Create &c, uint64_t maxu, srt_err *e2) {
     p->lvl_nt = !(c.knobs.lvl_nt.set && c.knobs.lvl_nt.v == 0);
     p->lvl_sp = !(c.knobs.lvl_sp.set && c.knobs.lvl_sp.v == 0);
     p->lvl_dyn = !(c.knobs.lvl_dyn.set && c.knobs.lvl_dyn.v == 0);
+    p->lvl_pack = 0;  // the probe rows: the unpacked row (the run's row is chosen with its bound, choose_family)
     // complete graphs in identity rows whose pairs mirror exactly (the
     // latencies here, over every pair; the losses too when they are on
     // the device, else the one-call build checks the losses it
@@ -960,8 +963,18 @@ srt_status choose_family(Create &c) {
         p->kp.lat32 = true;
         p->key_type = p->lvl_q ? srt::KEY_U32 : srt::KEY_U16;
         c.f16 = false;
+        // the LDS row: packed where that doubles the workgroups a CU (the
+        // runtime asked only where the layout is valid and not switched off)
+        const bool ask = !p->lvl_q && p->kp.lmax <= 14 && p->lvl_sp && !(c.knobs.lvl_pack.set && c.knobs.lvl_pack.v == 0);
+        const int fit_rt = ask ? srt::level_pack_fit(p->V, p->lvl_nt) : 0;
+        p->lvl_pack = srt::choose_row_packed(p->lvl_q != 0, p->kp.lmax, p->lvl_sp, c.knobs.lvl_pack,
+                                             srt::level_rows_per_cu(p->V, false, false),
+                                             srt::level_rows_per_cu(p->V, false, true), fit_rt)
+                          ? 2u
+                          : 0u;
+        p->lvl_spread = !(c.knobs.lvl_spread.set && c.knobs.lvl_spread.v == 0);
         p->desc = srt::describe_level(p->kp.g, p->lvl_q, p->kp.lmax, p->V, n, c.lvl_visits, p->lvl_sym,
-                                      p->d_lat16 != nullptr);
+                                      p->d_lat16 != nullptr, p->lvl_pack != 0);
     } else {
         p->lvl_q = 0;
         p->lvl_sym = p->lvl_sym_lat = false;
@@ -2230,8 +2243,9 @@ srt_status build_multi_level(srt_plan *p0, const std::vector<int32_t> &devs, srt
             dst = (unsigned long long *)dev_alloc(4 * 8);
             // the quantized solve's per-workgroup scratch: every rank its own
             // (ranks sharing a device run concurrently)
-            if (quant) c.lmem = (uint16_t *)dev_alloc(srt::level_scratch_bytes(devs[r], p0->V, true));
-            if (!s16 || (mode != 3 && !sloss) || !dst || (quant && !c.lmem)) e = hipErrorOutOfMemory;
+            // (and the packed row's members, the same way)
+            if (quant || c.pack) c.lmem = (uint16_t *)dev_alloc(srt::level_scratch_bytes(devs[r], p0->V, quant, c.pack));
+            if (!s16 || (mode != 3 && !sloss) || !dst || ((quant || c.pack) && !c.lmem)) e = hipErrorOutOfMemory;
         }
         if (e == hipSuccess && rows) {
             srt::level_stats_init(dst, st);

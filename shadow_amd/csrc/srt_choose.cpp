@@ -450,10 +450,21 @@ FrontierOrder frontier_vertex_order(const srt_csr *g, const uint32_t *nodes, uin
     return r;
 }
 
+bool choose_row_packed(bool quant, uint64_t lmax, bool sp, const Knob<int> &pack, int rows_unpacked, int rows_packed,
+                       int fit_rt) {
+    const bool valid = !quant && lmax <= 14 && sp && fit_rt >= 2;
+    if (!valid || (pack.set && pack.v == 0)) return false;
+    if (pack.set && pack.v == 1) return true;
+    return rows_unpacked < 2 && rows_packed >= 2;
+}
+
 std::string describe_level(uint64_t g, uint32_t q, uint64_t lmax, uint32_t V, uint32_t n, uint64_t visits, bool sym,
-                           bool lat16) {
+                           bool lat16, bool packed) {
     char d[200];
-    const char *rows = sym ? (lat16 ? " rows=sym lat16" : " rows=sym") : "";
+    const char *rows = sym ? (packed  ? (lat16 ? " rows=sym lat16 row=packed" : " rows=sym row=packed")
+                              : lat16 ? " rows=sym lat16"
+                                      : " rows=sym")
+                           : (packed ? " row=packed" : "");
     if (q)
         std::snprintf(d, sizeof d, "level:u32 g=%llu q=%u lmax=%llu(probe) V=%u n=%u visits=%llu loss=in-solve%s",
                       (unsigned long long)g, q, (unsigned long long)lmax, V, n, (unsigned long long)visits, rows);

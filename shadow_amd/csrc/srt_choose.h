@@ -32,6 +32,8 @@ struct CreateKnobs {
     Knob<int> lvl_nt;             // SRT_LVL_NT: 0 = the level solve's table rows by plain stores (A/B, tests)
     Knob<int> lvl_sp;             // SRT_LVL_SP: 0 = its per-item walk, not the pipelined one (A/B, tests)
     Knob<int> lvl_dyn;            // SRT_LVL_DYN: 0 = its rows dealt statically, not by a counter (A/B, tests)
+    Knob<int> lvl_pack;           // SRT_LVL_PACK: 0 = never its packed LDS row, 1 = wherever the layout is valid (A/B, tests)
+    Knob<int> lvl_spread;         // SRT_LVL_SPREAD: 0 = the packed row's small levels one lane group an item (A/B)
     Knob<int> fw_p1;              // SRT_FW_P1: u16/f16 phase 1, 1 = two FW steps per barrier, 0 = one (A/B)
     Knob<int> fw_emulate_ranks;   // SRT_FW_EMULATE_RANKS: rank 0's share of an N-rank schedule (measurement only)
     Knob<bool> fw_band;           // SRT_FW_BAND=1: grouped launches in banded tile order
@@ -118,9 +120,20 @@ struct FrontierOrder {
 FrontierOrder frontier_vertex_order(const srt_csr *g, const uint32_t *nodes, uint32_t n, std::vector<uint64_t> *in_ptr,
                                     std::vector<InEdge> *in_edge);
 
+// The LDS row of an integer level plan: packed (4.5 B a vertex, two 512-thread
+// workgroups a CU) or not.  The layout is valid for a plan that is not
+// quantized, whose bound is <= 14 (4-bit levels), with the pipelined walk on,
+// and whose packed kernel the runtime keeps two workgroups a CU of (fit_rt:
+// level_pack_fit).  Knob 0: never; 1: wherever valid; unset: where it doubles
+// the rows a CU -- the unpacked row allows fewer than two workgroups a CU by
+// the launch's arithmetic (rows_unpacked: level_rows_per_cu) and the packed
+// row two (rows_packed).
+bool choose_row_packed(bool quant, uint64_t lmax, bool sp, const Knob<int> &pack, int rows_unpacked, int rows_packed,
+                       int fit_rt);
+
 // describe() of a plan, by family
 std::string describe_level(uint64_t g, uint32_t q, uint64_t lmax, uint32_t V, uint32_t n, uint64_t visits, bool sym,
-                           bool lat16);
+                           bool lat16, bool packed = false);
 std::string describe_fw(bool f16, int key_type, const KeyParams &kp, bool complete, uint64_t ecc_units, uint32_t V,
                         uint32_t n, bool glds, bool band);
 std::string describe_sssp(uint64_t g, uint32_t V, uint32_t n, uint64_t n_in, uint32_t R, uint32_t groups,

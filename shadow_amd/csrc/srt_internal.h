@@ -356,6 +356,8 @@ struct srt_plan {
     uint32_t lvl_emu_ranks = 0;      // measurement (srt_plan_shard_rows + SRT_LVL_SHARD_EMU=1): rank row0's slice
     bool lvl_emu_built = false;      // ... every slice built once (the first run); later runs rebuild the own one
     unsigned long long *d_rowctr = nullptr;  // level solve: the rows dealt by a counter (LevelCtx::row_ctr)
+    uint32_t lvl_pack = 0;                   // the packed LDS row: its workgroups a CU (0: the unpacked row), chosen at create (choose_row_packed)
+    bool lvl_spread = true;                  // ... with K lane groups an item in small levels (knob SRT_LVL_SPREAD=0: one)
     bool lvl_nt = true, lvl_sp = true, lvl_dyn = true;  // its launch knobs, read at create (CreateKnobs): LevelCtx::nt_store, sp, row_ctr
     unsigned long long *d_lvisit = nullptr;  // level solve: class entries the last run walked
     uint32_t lvl_q = 0, lvl_rb = 0, lvl_vb = 0;  // quantized level solve: bucket width (units), entry field bits
@@ -499,11 +501,13 @@ struct LevelCtx {
     float *out_loss = nullptr;
     unsigned long long *visits = nullptr;  // class entries walked (nullable)
     uint32_t q = 0, rb = 0, vb = 0;        // quantized solve: bucket width (units), remainder / vertex bits of an entry
-    uint16_t *lmem = nullptr;              // quantized solve: level_scratch_bytes of per-workgroup scratch
+    uint16_t *lmem = nullptr;              // quantized solve, packed row: level_scratch_bytes of per-workgroup scratch
     bool idn = false;                      // nodes[j] = j, n = V, n % 4 == 0: the vectorised row output
     unsigned long long *row_ctr = nullptr; // level solve: {next row, workgroups done}, 0 between launches (nullable: rows dealt statically)
     bool nt_store = true;                  // table rows by non-temporal stores
     bool sp = true;                        // the pipelined class walk (false: the per-item walk)
+    uint32_t pack = 0;                     // packed-row workgroups a CU (srt_plan::lvl_pack; 0: the unpacked row); needs lmem
+    bool spread = true;                    // packed row: K lane groups an item in small levels
 };
 LevelCtx level_ctx(srt_plan *p);
 // the class CSRs of a level plan at its bound (the run's first step)
@@ -514,8 +518,14 @@ srt_status level_prepare(srt_plan *p, srt_err *err);
 // c.stream
 void level_solve_stage(const LevelCtx &c, uint32_t r0, uint32_t r1, uint32_t lmax, void *stage_lat,
                        float *stage_loss, uint32_t stage_mode, unsigned long long *d_stats);
-// bytes of the quantized solve's scratch on `device` for V vertices (0 unless quant)
-size_t level_scratch_bytes(int device, uint32_t V, bool quant);
+// bytes of the per-workgroup scratch on `device` for V vertices: the quantized
+// solve's, or the packed row's at `pack` workgroups a CU (0 when neither)
+size_t level_scratch_bytes(int device, uint32_t V, bool quant, uint32_t pack = 0);
+// the LDS rows of V vertices a CU holds by the launch's own arithmetic, and the
+// packed-row workgroups the runtime keeps resident on a CU of the current
+// device (the kernel's registers and its real dynamic LDS; 0: the query failed)
+int level_rows_per_cu(uint32_t V, bool quant, bool packed);
+int level_pack_fit(uint32_t V, bool nt_store);
 // bits of a vertex index < V in a quantized class entry
 uint32_t level_vbits(uint32_t V);
 // the shortest non-self-loop edge latency of the plan's uploaded graph, ns

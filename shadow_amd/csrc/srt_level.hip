@@ -414,7 +414,25 @@ __constant__ uint32_t lvl_diag;                // level solve ablations (SRT_LVL
 // at probe[0] += the edges walked.
 // SP (VW = 2): the class lists walked as one stream of chunks a lane group,
 // software-pipelined (see the walk below).
-template <int LPT, int UNR, uint32_t CLSN, int VW, bool NT, bool SP = false>
+// PK (SP, CLSN 16, lcap <= PACK_LMAX): the packed row of srt_rowfold.h, 4.5 B
+// a vertex, so that two 512-thread workgroups share a CU where the 8-B row
+// allows one of 1,024 (16k vertices: 73,984 B against 131,328).  A 5-B row (u8
+// level + f32 loss) does not fit twice: 2 x (256 + 5 x 16,384 + 544 B static)
+// = 165,440 B > 163,840; nor do two workgroups of 1,024 threads: 8 waves a SIMD
+// allow 64 VGPRs and the walk holds 104.  A vertex's key takes a hit's
+// candidate by one atomicMin(1 << 30 | loss bits): state 3 -> 1 and the min
+// over the tight in-edges at once (no level store a hit); a settled key (state
+// 0) is below every candidate and skipped by its state.  The candidate's bits
+// are masked to 30, so the state is exact whatever the losses are; the table's
+// bits are the unpacked row's for losses in [0, 1], which every path to a plan
+// enforces before a result is returned: the host scan (CsrStats::badloss_k,
+// srt_api.cpp reference_errors), or -- the losses left to the device --
+// first_bad_loss / the device range check (join_loss_check), whose error
+// replaces the build's result.  The collect pass moves the keys of state 1 to
+// state 0 and writes their 4-bit levels, a thread the word of its own quad
+// (plain stores); the members go to mem_all + blockIdx.x * V (L2-resident, as
+// level_q_kernel's).  spread: K lane groups an item in small levels (below).
+template <int LPT, int UNR, uint32_t CLSN, int VW, bool NT, bool SP = false, bool PK = false>
 __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
     uint32_t V, const uint32_t *__restrict__ nodes, uint32_t n, uint32_t row0, uint32_t row1,
     const uint32_t *__restrict__ cls_out, const uint32_t *__restrict__ cls_in, const uint64_t *__restrict__ ce_out,
@@ -422,7 +440,9 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
     const float *__restrict__ sl_loss, uint64_t *__restrict__ out_lat, float *__restrict__ out_loss,
     unsigned long long *stats, const uint32_t *__restrict__ row_list, void *__restrict__ out32,
     float *__restrict__ out32_loss, bool stage16, uint32_t *__restrict__ probe,
-    unsigned long long *__restrict__ visit_cnt, bool idn, unsigned long long *row_ctr) {
+    unsigned long long *__restrict__ visit_cnt, bool idn, unsigned long long *row_ctr, uint16_t *mem_all,
+    bool spread) {
+    static_assert(!PK || (SP && CLSN == 16), "the packed row: the pipelined walk, levels <= PACK_LMAX");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ unsigned long long red_min[16], red_cnt[16], red_vis[16];
     __shared__ uint32_t dyn_k;
@@ -435,7 +455,10 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
     uint32_t *hist = reinterpret_cast<uint32_t *>(smem);  // hist[l]: end of level l in mem (l <= 31)
     uint16_t *lrow = reinterpret_cast<uint16_t *>(smem + SOLVE_HIST);
     uint32_t *prow = reinterpret_cast<uint32_t *>(smem + lds_prow_off(SOLVE_HIST, V));
-    uint16_t *mem = reinterpret_cast<uint16_t *>(smem + lds_mem_off(SOLVE_HIST, V));
+    uint16_t *mem = PK ? mem_all + (uint64_t)blockIdx.x * V : reinterpret_cast<uint16_t *>(smem + lds_mem_off(SOLVE_HIST, V));
+    uint32_t *key = reinterpret_cast<uint32_t *>(smem + SOLVE_HIST);  // PK: state | loss bits
+    uint16_t *lev = reinterpret_cast<uint16_t *>(smem + pack_lev_off(V));  // PK: the levels of quad k in word k
+    auto lev_of = [&](uint32_t v) -> uint32_t { return ((uint32_t)lev[v >> 2] >> (4 * (v & 3u))) & 0xfu; };
     const uint16_t LINF = 0xffffu;
     const uint32_t FINF = 0x7f800000u;  // +inf bits
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
@@ -467,6 +490,19 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
 #endif
         // 1. every vertex unreached, s at level 0 (petgraph's zero score);
         // four vertices a thread a step (8-B level and 16-B loss stores)
+        if constexpr (PK) {
+            // (the last quad's vertices past V stay unreached / 0xF: never read)
+            for (uint32_t v4 = 4 * tid; v4 < V; v4 += 4 * nt) {
+                const uint32_t q = s - v4;  // s among them: state 0, loss 0, level 0
+                lev[v4 >> 2] = (uint16_t)(q < 4u ? 0xffffu & ~(0xfu << (4 * q)) : 0xffffu);
+                if (v4 + 3 < V) {
+                    *reinterpret_cast<uint4 *>(key + v4) =
+                        make_uint4(q == 0 ? 0u : ~0u, q == 1 ? 0u : ~0u, q == 2 ? 0u : ~0u, q == 3 ? 0u : ~0u);
+                } else {
+                    for (uint32_t v = v4; v < V; ++v) key[v] = v == s ? 0u : ~0u;
+                }
+            }
+        } else
         for (uint32_t v4 = 4 * tid; v4 < V; v4 += 4 * nt) {
             if (v4 + 3 < V) {
                 uint2 lw = make_uint2(0xffffffffu, 0xffffffffu);
@@ -503,7 +539,41 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
         auto compact = [&](uint16_t want, uint32_t at, uint32_t par, int ci) {
             for (uint32_t v4 = 4 * tid; v4 < V; v4 += 4 * nt) {
                 uint32_t fm = 0;
-                if (v4 + 3 < V) {
+                if constexpr (PK) {
+                    const uint32_t in = V - v4 >= 4u ? 0xfu : (1u << (V - v4)) - 1u;  // the quad's vertices < V
+                    const uint32_t lw = lev[v4 >> 2];
+                    if (want == LINF) {  // unsettled: the level still 0xF
+                        fm = ((uint32_t)((lw & 0xfu) == 0xfu) | (uint32_t)((lw & 0xf0u) == 0xf0u) << 1 |
+                              (uint32_t)((lw & 0xf00u) == 0xf00u) << 2 | (uint32_t)((lw & 0xf000u) == 0xf000u) << 3) & in;
+                    } else {  // entered this level (state 1): settled, the state cleared, the level written
+                        uint32_t nl = lw;
+                        uint32_t kv[4];
+                        if (in == 0xfu) {
+                            const uint4 k4 = *reinterpret_cast<const uint4 *>(key + v4);
+                            kv[0] = k4.x, kv[1] = k4.y, kv[2] = k4.z, kv[3] = k4.w;
+                        } else {
+#pragma unroll
+                            for (uint32_t q = 0; q < 4; ++q) kv[q] = (in >> q) & 1u ? key[v4 + q] : ~0u;
+                        }
+#pragma unroll
+                        for (uint32_t q = 0; q < 4; ++q)
+                            if ((kv[q] >> 30) == 1u) {
+                                fm |= 1u << q;
+                                kv[q] &= PACK_LOSS;
+                                nl = (nl & ~(0xfu << (4 * q))) | (uint32_t)want << (4 * q);
+                            }
+                        if (fm) {
+                            lev[v4 >> 2] = (uint16_t)nl;
+                            if (in == 0xfu) {
+                                *reinterpret_cast<uint4 *>(key + v4) = make_uint4(kv[0], kv[1], kv[2], kv[3]);
+                            } else {
+#pragma unroll
+                                for (uint32_t q = 0; q < 4; ++q)
+                                    if ((in >> q) & 1u) key[v4 + q] = kv[q];
+                            }
+                        }
+                    }
+                } else if (v4 + 3 < V) {
                     const uint2 w = *reinterpret_cast<const uint2 *>(lrow + v4);
                     fm = (uint32_t)((w.x & 0xffffu) == want) | (uint32_t)((w.x >> 16) == want) << 1 |
                          (uint32_t)((w.y & 0xffffu) == want) << 2 | (uint32_t)((w.y >> 16) == want) << 3;
@@ -613,8 +683,10 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                 // item, group g taking item g mod T's chunks g div T, + K, + 2K,
                 // ... (one item a group), so its few lists are walked in one or
                 // two steps instead of one chunk a step by one group (C3 4.40 ->
-                // 4.26 ms; C2's 4 workgroups a CU: 0.334 -> 0.351 ms, so not there)
-                const uint32_t K = nt == LOSS_NT && 2 * T <= ngrp ? ngrp / T : 1u;
+                // 4.26 ms; C2's 4 workgroups a CU: 0.334 -> 0.351 ms, so not there;
+                // the packed row's two workgroups a CU: C3 solve 4.225 -> 4.194 ms,
+                // so there too -- `spread`)
+                const uint32_t K = (PK ? spread : nt == LOSS_NT) && 2 * T <= ngrp ? ngrp / T : 1u;
                 const uint32_t CHS = K * CH;  // a group's chunk stride in an item
                 uint32_t ct = K > 1 ? (grp < T * K ? grp % T : T) : grp, cw = 1, cx = 0, ce0 = 0, ce1 = 0;
                 uint32_t pw = 1, px = 0, pe0 = 0, pe1 = 0;  // the group's next item
@@ -653,40 +725,74 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                         }
 #pragma unroll
                         for (int q = 0; q < NE; ++q) o[q] = ok[q] ? (uint32_t)wd[q] : 0u;
-                        uint16_t lo_[NE];
+                        if constexpr (PK) {
 #pragma unroll
-                        for (int q = 0; q < NE; ++q) lo_[q] = lrow[o[q]];
+                            for (int q = 0; q < NE; ++q) visits += ok[q];
+                            if ((pm >> cw) & 1ull) {
+                                // push: the head's key, unless settled (state 0),
+                                // takes state 1 and the min of the candidates
+                                uint32_t ko[NE];
 #pragma unroll
-                        for (int q = 0; q < NE; ++q) visits += ok[q];
-                        if ((pm >> cw) & 1ull) {
-                            // push: x in N_j, its class-w out-edges x -> v, v
-                            // unsettled or at l: v enters level l (stored once),
-                            // its loss min-folded by an LDS atomic
-                            const float onem = 1.0f - __uint_as_float(prow[cx]);
+                                for (int q = 0; q < NE; ++q) ko[q] = key[o[q]];
+                                const float onem = 1.0f - __uint_as_float(key[cx] & PACK_LOSS);
 #pragma unroll
-                            for (int q = 0; q < NE; ++q)
-                                if (ok[q] && lo_[q] >= (uint16_t)l) {
-                                    const float r = __uint_as_float((uint32_t)(wd[q] >> 32));
-#if LOSS_COUNT
-                                    if (!(lvl_diag & 2) && lo_[q] > (uint16_t)l) lrow[o[q]] = (uint16_t)l;
-                                    if (!(lvl_diag & 1))
-                                        atomicMin(&prow[o[q]], __float_as_uint(1.0f - __fmul_rn(onem, r)));
-#else
-                                    if (lo_[q] > (uint16_t)l) lrow[o[q]] = (uint16_t)l;
-                                    atomicMin(&prow[o[q]], __float_as_uint(1.0f - __fmul_rn(onem, r)));
-#endif
-                                }
+                                for (int q = 0; q < NE; ++q)
+                                    if (ok[q] && (ko[q] >> 30)) {
+                                        const float r = __uint_as_float((uint32_t)(wd[q] >> 32));
+                                        const uint32_t c = __float_as_uint(1.0f - __fmul_rn(onem, r));
+                                        atomicMin(&key[o[q]], 1u << 30 | (c & PACK_LOSS));
+                                    }
+                            } else {
+                                // pull: the tail's 4-bit level against j; a tail at j is settled
+                                const uint32_t j = l - cw;
+                                uint32_t lo4[NE];
+#pragma unroll
+                                for (int q = 0; q < NE; ++q) lo4[q] = lev_of(o[q]);
+#pragma unroll
+                                for (int q = 0; q < NE; ++q)
+                                    if (ok[q] && lo4[q] == j) {
+                                        const float r = __uint_as_float((uint32_t)(wd[q] >> 32));
+                                        const float lu = __uint_as_float(key[o[q]] & PACK_LOSS);
+                                        const uint32_t c = __float_as_uint(1.0f - __fmul_rn(1.0f - lu, r));
+                                        atomicMin(&key[cx], 1u << 30 | (c & PACK_LOSS));
+                                    }
+                            }
                         } else {
-                            // pull: x unsettled, its class-w in-edges u -> x, u in N_j
-                            const uint32_t j = l - cw;
+                            uint16_t lo_[NE];
 #pragma unroll
-                            for (int q = 0; q < NE; ++q)
-                                if (ok[q] && lo_[q] == (uint16_t)j) {
-                                    const float r = __uint_as_float((uint32_t)(wd[q] >> 32));
-                                    lrow[cx] = (uint16_t)l;
-                                    const float c = 1.0f - __fmul_rn(1.0f - __uint_as_float(prow[o[q]]), r);
-                                    atomicMin(&prow[cx], __float_as_uint(c));
-                                }
+                            for (int q = 0; q < NE; ++q) lo_[q] = lrow[o[q]];
+#pragma unroll
+                            for (int q = 0; q < NE; ++q) visits += ok[q];
+                            if ((pm >> cw) & 1ull) {
+                                // push: x in N_j, its class-w out-edges x -> v, v
+                                // unsettled or at l: v enters level l (stored once),
+                                // its loss min-folded by an LDS atomic
+                                const float onem = 1.0f - __uint_as_float(prow[cx]);
+#pragma unroll
+                                for (int q = 0; q < NE; ++q)
+                                    if (ok[q] && lo_[q] >= (uint16_t)l) {
+                                        const float r = __uint_as_float((uint32_t)(wd[q] >> 32));
+#if LOSS_COUNT
+                                        if (!(lvl_diag & 2) && lo_[q] > (uint16_t)l) lrow[o[q]] = (uint16_t)l;
+                                        if (!(lvl_diag & 1))
+                                            atomicMin(&prow[o[q]], __float_as_uint(1.0f - __fmul_rn(onem, r)));
+#else
+                                        if (lo_[q] > (uint16_t)l) lrow[o[q]] = (uint16_t)l;
+                                        atomicMin(&prow[o[q]], __float_as_uint(1.0f - __fmul_rn(onem, r)));
+#endif
+                                    }
+                            } else {
+                                // pull: x unsettled, its class-w in-edges u -> x, u in N_j
+                                const uint32_t j = l - cw;
+#pragma unroll
+                                for (int q = 0; q < NE; ++q)
+                                    if (ok[q] && lo_[q] == (uint16_t)j) {
+                                        const float r = __uint_as_float((uint32_t)(wd[q] >> 32));
+                                        lrow[cx] = (uint16_t)l;
+                                        const float c = 1.0f - __fmul_rn(1.0f - __uint_as_float(prow[o[q]]), r);
+                                        atomicMin(&prow[cx], __float_as_uint(c));
+                                    }
+                            }
                         }
                     }
                     ct = nt2;
@@ -764,10 +870,10 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
         __syncthreads();  // hist / lrow final for the output
         LOSS_TICK(6)
         // 3. table row i (or staging slot k), or the probe's row maximum
-        if (probe) {
+        if (probe) {  // (probe rows run the unpacked row: their caps are 15, 31, 63)
             uint32_t rmax = 0;
             for (uint32_t j0 = tid; j0 < n; j0 += nt) {
-                const uint32_t l = lrow[nodes[j0]];
+                const uint32_t l = PK ? lev_of(nodes[j0]) : lrow[nodes[j0]];
                 rmax = l > rmax ? l : rmax;
             }
             for (int off = 32; off > 0; off >>= 1) {
@@ -798,10 +904,17 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
             typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
             typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
             for (uint32_t j4 = 4 * tid; j4 < n; j4 += 4 * nt) {
-                const uint2 lw = *reinterpret_cast<const uint2 *>(lrow + j4);
-                const uint4 pw = *reinterpret_cast<const uint4 *>(prow + j4);
-                const uint32_t lv[4] = {lw.x & 0xffffu, lw.x >> 16, lw.y & 0xffffu, lw.y >> 16};
-                const uint32_t pv[4] = {pw.x, pw.y, pw.z, pw.w};
+                // (PK: one 2-B word of levels, 0xF = unreached, and the 16 B of keys)
+                const uint32_t l4 = PK ? lev[j4 >> 2] : 0u;
+                const uint2 lw = PK ? make_uint2(0u, 0u) : *reinterpret_cast<const uint2 *>(lrow + j4);
+                const uint4 pw = *reinterpret_cast<const uint4 *>((PK ? key : prow) + j4);
+                auto lv4 = [&](int q) -> uint32_t {
+                    const uint32_t x = (l4 >> (4 * q)) & 0xfu;
+                    return x == 0xfu ? (uint32_t)LINF : x;
+                };
+                const uint32_t lv[4] = {PK ? lv4(0) : lw.x & 0xffffu, PK ? lv4(1) : lw.x >> 16,
+                                        PK ? lv4(2) : lw.y & 0xffffu, PK ? lv4(3) : lw.y >> 16};
+                const uint32_t pv[4] = {pw.x, pw.y, pw.z, pw.w};  // (PK: settled keys, the loss bits as they are)
                 uint64_t lu[4], latv[4];
                 float lossv[4];
 #pragma unroll
@@ -864,7 +977,7 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                     lossv = sl_loss[j];
                     lu = latv == ~0ull ? ~0ull : latv / g;
                 } else {
-                    const uint16_t l = lrow[vv[q]];
+                    const uint16_t l = PK ? (lev_of(vv[q]) == 0xfu ? LINF : (uint16_t)lev_of(vv[q])) : lrow[vv[q]];
                     if (l == LINF) {
                         ++unreach;
                         latv = lu = ~0ull;
@@ -872,7 +985,7 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                     } else {
                         lu = l;
                         latv = lu * g;
-                        lossv = __uint_as_float(prow[vv[q]]);
+                        lossv = __uint_as_float(PK ? key[vv[q]] : prow[vv[q]]);
                     }
                 }
                 // streamed out without allocating in the caches (NT): the
@@ -1283,6 +1396,8 @@ LevelCtx level_ctx(srt_plan *p) {
     c.idn = p->ident_nodes && p->n == p->V && p->n % 4 == 0;
     c.nt_store = p->lvl_nt;
     c.sp = p->lvl_sp;
+    c.pack = p->lvl_pack;
+    c.spread = p->lvl_spread;
     // rows dealt by a counter (knob SRT_LVL_DYN=0: statically, A/B)
     const bool dyn = p->lvl_dyn;
     if (dyn && !p->d_rowctr) {
@@ -1301,6 +1416,12 @@ uint32_t level_vbits(uint32_t V) {
     uint32_t vb = 1;
     while ((1u << vb) < V) ++vb;
     return vb;
+}
+
+// level_grid's arithmetic: the workgroups whose LDS rows a CU holds (160 KB,
+// 2 KB a workgroup for its static LDS and the allocation's granule)
+int level_rows_per_cu(uint32_t V, bool quant, bool packed) {
+    return (int)((160 * 1024) / (solve_lds_bytes(V, quant, packed) + 2048));
 }
 
 namespace {
@@ -1520,16 +1641,26 @@ srt_status level_csr_sharded(srt_plan *p, uint64_t wmax, bool with_loss, uint32_
     return SRT_OK;
 }
 
+// the packed row's instantiation (16 class offsets, the pipelined walk)
+auto pick_packed_kernel(bool nt_store) {
+    return nt_store ? level_solve_kernel<4, 4, 16, 2, true, true, true> : level_solve_kernel<4, 4, 16, 2, false, true, true>;
+}
+
 // Workgroups of a level solve launch over `rows` rows (one row per
 // workgroup at a time; the LDS row decides how many fit a CU)
-uint32_t level_grid(int device, uint32_t V, bool quant, uint32_t rows, uint32_t *nt_out) {
-    const size_t lds = solve_lds_bytes(V, quant);
+uint32_t level_grid(int device, uint32_t V, bool quant, uint32_t rows, uint32_t *nt_out, uint32_t pack) {
+    // the packed row: PACK_NT threads a workgroup, `pack` workgroups a CU (what
+    // the runtime said of the kernel's registers and this LDS row at the create)
+    if (pack) {
+        if (nt_out) *nt_out = PACK_NT;
+        return std::max<uint32_t>(1, std::min<uint32_t>(rows, (uint32_t)cu_count(device) * pack));
+    }
     // workgroups a CU's LDS holds, then the fewest threads a workgroup (256,
     // 512 or 1024) that still fill the CU's 2,048 thread slots: more rows in
     // flight a CU for small graphs (C2, 4k: 4 x 512 threads 0.39 ms a solve
     // against 2 x 1024 0.50 ms; 4 x 256 0.39), one 1,024-thread workgroup for
     // C3's 128 KB rows
-    const int lds_cu = (int)std::max<size_t>(1, (160 * 1024) / (lds + 2048));
+    const int lds_cu = std::max(1, level_rows_per_cu(V, quant, false));
     uint32_t nt = 256;
     while (nt < LOSS_NT && (int)(2048 / nt) > lds_cu) nt *= 2;
     const int per_cu = std::max(1, std::min(2048 / (int)nt, lds_cu));
@@ -1575,9 +1706,12 @@ void launch_solve_ctx(const LevelCtx &c, unsigned long long *d_stats, const uint
     const uint32_t V = c.V, rows = list ? r1 : r1 - r0;
     if (!rows) return;
     const bool quant = c.q != 0;
+    // the packed row: table and staged rows of a plan that chose it (the probe
+    // rows' caps are past its 4-bit levels)
+    const uint32_t pack = !quant && !probe && c.sp && c.t_cls == 16 && lcap <= PACK_LMAX && c.lmem ? c.pack : 0u;
     uint32_t nt = 0;
-    const uint32_t grid = level_grid(c.device, V, quant, rows, &nt);
-    const size_t lds = solve_lds_bytes(V, quant);
+    const uint32_t grid = level_grid(c.device, V, quant, rows, &nt, pack);
+    const size_t lds = solve_lds_bytes(V, quant, pack != 0);
     const uint64_t vc1 = (uint64_t)V * c.t_cls + 1;
     const uint32_t *co = c.tcls, *ci = c.tcls + vc1;
     const uint64_t *eo = c.ce_out, *ei = c.ce_in;
@@ -1595,19 +1729,19 @@ void launch_solve_ctx(const LevelCtx &c, unsigned long long *d_stats, const uint
                            list, stage, stage_loss, stage_mode, probe, c.visits, c.lmem);
         return;
     }
-    const auto kern = pick_solve_kernel(c.t_cls, c.nt_store, c.sp);
+    const auto kern = pack ? pick_packed_kernel(c.nt_store) : pick_solve_kernel(c.t_cls, c.nt_store, c.sp);
     (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BUDGET - 4096));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(nt), lds, c.stream, V, c.nodes, c.n, list ? 0u : r0, r1, co, ci, eo, ei,
                        lcap, c.g, c.sl_lat, c.sl_loss, c.out_lat, c.out_loss, d_stats, list,
                        stage_mode ? stage : nullptr, stage_mode ? stage_loss : nullptr, stage_mode == 1, probe,
-                       c.visits, c.idn, c.row_ctr);
+                       c.visits, c.idn, c.row_ctr, pack ? c.lmem : (uint16_t *)nullptr, c.spread);
 }
 
-// the per-workgroup scratch of the quantized solve (p->d_lmem): every
-// workgroup a launch may have, V u16 each
+// the per-workgroup scratch of the quantized solve and of the packed row
+// (p->d_lmem): every workgroup a launch may have, V u16 each
 srt_status level_scratch(srt_plan *p, srt_err *err) {
-    if (!p->lvl_q) return SRT_OK;
-    return grow(&p->d_lmem, &p->lmem_cap, level_scratch_bytes(p->device, p->V, true) / 2, err,
+    if (!p->lvl_q && !p->lvl_pack) return SRT_OK;
+    return grow(&p->d_lmem, &p->lmem_cap, level_scratch_bytes(p->device, p->V, p->lvl_q != 0, p->lvl_pack) / 2, err,
                 "hipMalloc(level scratch)");
 }
 
@@ -1748,8 +1882,21 @@ void level_solve_stage(const LevelCtx &c, uint32_t r0, uint32_t r1, uint32_t lma
     launch_solve_ctx(c, d_stats, nullptr, r0, r1, lmax, false, nullptr, stage_lat, stage_loss, stage_mode);
 }
 
-size_t level_scratch_bytes(int device, uint32_t V, bool quant) {
-    return quant ? (size_t)level_grid(device, V, true, ~0u, nullptr) * V * 2 : 0;
+size_t level_scratch_bytes(int device, uint32_t V, bool quant, uint32_t pack) {
+    return quant || pack ? (size_t)level_grid(device, V, quant, ~0u, nullptr, quant ? 0u : pack) * V * 2 : 0;
+}
+
+int level_pack_fit(uint32_t V, bool nt_store) {
+    const auto kern = pick_packed_kernel(nt_store);
+    int wgs = 0;
+    if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BUDGET - 4096)) !=
+            hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, kern, (int)PACK_NT, solve_lds_bytes(V, false, true)) !=
+            hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return wgs;
 }
 
 void level_loss_index(srt_plan *p, uint32_t *d_idx, uint64_t cap, unsigned long long *d_cnt, hipStream_t s) {

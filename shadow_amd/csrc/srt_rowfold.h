@@ -47,8 +47,21 @@ __host__ __device__ constexpr size_t up16(size_t b) { return (b + 15) & ~(size_t
 __host__ __device__ constexpr size_t lds_prow_off(size_t hist, size_t V) { return hist + up16(V * 2); }
 __host__ __device__ constexpr size_t lds_mem_off(size_t hist, size_t V) { return lds_prow_off(hist, V) + V * 4; }
 __host__ __device__ constexpr size_t fold_lds_bytes(size_t V) { return lds_mem_off(HIST_BYTES, V) + V * 2; }
-__host__ __device__ constexpr size_t solve_lds_bytes(size_t V, bool quant) {
-    return quant ? SOLVE_HIST + V * 8 : lds_mem_off(SOLVE_HIST, V) + up16(V * 2);
+// The packed row of the integer level solve (levels <= PACK_LMAX): `hist`,
+// then one u32 key a vertex at SOLVE_HIST -- the loss's f32 bits in the low 30
+// (a loss in [0, 1]: bits <= 0x3f800000), the state in the top 2 (3 unreached:
+// the initial key is all ones; 1 entered the level being built; 0 settled, the
+// loss final) -- then one 4-bit level a vertex (0xF until settled), the four
+// vertices 4 k .. 4 k + 3 in the u16 word k at pack_lev_off.  4.5 B a vertex;
+// the members live in a per-workgroup global scratch (level_scratch_bytes).
+constexpr uint32_t PACK_LMAX = 14;      // the largest level a 4-bit field holds beside 0xF
+constexpr uint32_t PACK_LOSS = 0x3fffffffu;  // a key's loss bits
+constexpr uint32_t PACK_NT = 512;       // threads of a packed-row workgroup (two a CU: 4 waves a SIMD)
+__host__ __device__ constexpr size_t pack_lev_off(size_t V) { return SOLVE_HIST + up16(V * 4); }
+__host__ __device__ constexpr size_t solve_lds_bytes(size_t V, bool quant, bool packed = false) {
+    return quant    ? SOLVE_HIST + V * 8
+           : packed ? pack_lev_off(V) + up16((V + 3) / 4 * 2)
+                    : lds_mem_off(SOLVE_HIST, V) + up16(V * 2);
 }
 
 template <typename K>
