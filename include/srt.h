@@ -245,9 +245,11 @@ typedef struct {
 } srt_pkt;
 
 /* PacketDeliveryStatusFlags (src/main/routing/packet.minimal.h:24-36): the send
- * decision's two and the inbound router stage's five */
+ * decision's two, the inbound router stage's five and the interface's one
+ * (PDS_SND_INTERFACE_SENT, packet.minimal.h:21) of the outbound relay stage */
 enum {
     SRT_PDS_NONE = 0,
+    SRT_PDS_SND_INTERFACE_SENT = 1u << 7,
     SRT_PDS_INET_SENT = 1u << 8,
     SRT_PDS_INET_DROPPED = 1u << 9,
     SRT_PDS_ROUTER_ENQUEUED = 1u << 10,
@@ -323,8 +325,9 @@ srt_status srt_packet_events_status(srt_plan *plan, srt_err *err);
  * exact, state included, and a pure function of the arrival order, the deliver
  * times, the packet sizes and each host's download bandwidth.
  * OUT OF SCOPE: the CPU-delay model that reschedules events (host.rs:820-848),
- * the loopback relay and the outbound relay (is_local is always false here),
- * and anything the interface does after it receives the packet.
+ * the loopback relay (is_local is always false here; the outbound relay is the
+ * srt_outbound stage below), and anything the interface does after it receives
+ * the packet.
  * ABI: additive to version 4; detect the stage by its symbols. */
 typedef struct srt_inbound srt_inbound;
 
@@ -417,6 +420,149 @@ srt_status srt_inbound_state(srt_inbound *ib, srt_inbound_host_state *out, srt_e
 srt_status srt_inbound_control_law(srt_inbound *ib, const uint64_t *counts, uint64_t n, int use_table,
                                    uint64_t *increments, srt_err *err);
 void srt_inbound_destroy(srt_inbound *ib);
+
+/* --------------------------------------------------- outbound relay stage */
+/* What the source host does before Worker::send_packet, batched over hosts:
+ * the step that produces srt_pkt.t_ns and the per-host send order
+ * srt_packet_batch requires.  When a socket has data,
+ * notify_socket_has_packets (host/host.rs:988-1002) puts the socket into the
+ * interface's queuing discipline unless it is there already
+ * (networkinterface_wantsSend, host/network/network_interface.c:344-370) and
+ * notifies relay_inet_out: an Idle relay schedules its forward task at the
+ * current time (one host event id).  The task (Relay::forward_until_blocked,
+ * network/relay/mod.rs:200-272) takes the relay's cached packet if it holds
+ * one, else pops the interface (network_interface.c:205-340,
+ * network_queuing_disciplines.c):
+ *   FIFO (Q_DISC_MODE_FIFO, the default): of the sockets in the queue, the one
+ *     whose NEXT packet has the smallest priority (Host::get_next_packet_priority,
+ *     host.rs:715: distinct within a host); only socket heads are compared, a
+ *     socket is a FIFO of its packets whatever their priorities.  Equal
+ *     priorities within a host are a caller error: taken in arrival order.
+ *   round robin: the socket at the head of a plain queue, pushed to its tail
+ *     again if it still has data.
+ * The popped packet gets INTERFACE_SENT.  A packet whose destination is the
+ * interface's own address (SRT_OUT_LOCAL) is exempt from the bucket and is
+ * pushed back into the interface; every other packet, unless now <
+ * bootstrap_end_ns, needs conforming_remove(total_size) of a token bucket
+ * sized from bandwidth_up (host.rs:299-302, relay/mod.rs:277-287,
+ * relay/token_bucket.rs: 1 ms refills of max(1, bytes_per_second / 1000),
+ * capacity one refill + CONFIG_MTU, full at time 0): if that fails the packet
+ * is cached (RELAY_CACHED) and the task rescheduled after the returned
+ * duration (one more event id), else it gets RELAY_FORWARDED and goes through
+ * Router::push to Worker::send_packet at that moment (router/mod.rs:49-55,
+ * 74-77): send_ns is srt_pkt.t_ns.
+ * Event order at one host, the stage's contract: events run in time order, and
+ * at equal times every arrival (socket-has-data), in the caller's list order,
+ * runs before the forward task.  LIMIT: the reference orders local events of
+ * equal time by event id, which the library does not own; a caller whose
+ * socket-has-data events can follow a forward task of the same time must split
+ * the window there.
+ * The stage is exact, state included, and a pure function of each host's
+ * arrival list (ready_ns, socket, priority, size, local flag), the qdisc and
+ * bandwidth_up.
+ * OUT OF SCOPE: how sockets produce packets (TCP/UDP buffers, retransmission),
+ * the loopback relay, the CPU-delay model that reschedules events, and what the
+ * interface does with a local packet pushed back into it.
+ * ABI: additive to version 4; detect the stage by its symbols. */
+typedef struct srt_outbound srt_outbound;
+
+#define SRT_QDISC_FIFO 0
+#define SRT_QDISC_RR 1
+#define SRT_OUT_LOCAL 1u /* srt_out_pkt.flags: destination is the interface's own address */
+
+/* one packet a socket hands to the interface, 32 bytes */
+typedef struct {
+    uint64_t ready_ns;   /* time of the socket-has-data event */
+    uint64_t priority;   /* Host::get_next_packet_priority value */
+    uint32_t total_size; /* payload plus headers */
+    uint32_t socket;     /* < max_sockets, an index local to the host */
+    uint32_t flags;      /* SRT_OUT_LOCAL */
+    uint32_t reserved;
+} srt_out_pkt;
+
+/* a packet of an EARLIER call that was forwarded in this one, 32 bytes */
+typedef struct {
+    uint64_t seq;       /* its call's seq_base + its batch index */
+    uint64_t send_ns;
+    uint64_t send_rank; /* UINT64_MAX for a local packet */
+    uint32_t status;    /* SRT_PDS_* */
+    uint32_t src_host;
+} srt_outbound_late;
+
+/* one host's state (tests, checkpoints, event-id accounting) */
+typedef struct {
+    uint64_t balance;         /* TokenBucket */
+    uint64_t last_refill_ns;
+    uint64_t task_ns;         /* pending forward task; UINT64_MAX = relay Idle */
+    uint64_t tasks_scheduled; /* forward tasks scheduled so far: each took one host event id */
+    uint64_t sent_total;      /* non-local packets forwarded so far = the next send_rank */
+    uint64_t queue_len;       /* packets in the socket queues */
+    uint32_t cached;          /* 1: the relay holds a cached next_packet */
+    uint32_t overflow;        /* 1: this host's ring overflowed, its results are invalid */
+} srt_outbound_host_state;
+
+/* srt_outbound_status flags */
+#define SRT_OUTBOUND_RING_OVERFLOW 1u   /* a host held more unresolved packets than queue_cap */
+#define SRT_OUTBOUND_LATE_OVERFLOW 2u   /* more late records than late_cap (the rest are lost) */
+#define SRT_OUTBOUND_TIME_REGRESSION 4u /* an arrival earlier than the previous call's until_ns */
+#define SRT_OUTBOUND_OVERSIZE 8u        /* a non-local packet larger than its host's token bucket can
+                                           hold: the reference would reschedule it for ever; here
+                                           its forward task is tried once a call (task_ns moved to
+                                           until_ns) */
+#define SRT_OUTBOUND_AFTER_UNTIL 16u    /* an arrival at or after until_ns: not taken (status 0) */
+#define SRT_OUTBOUND_BAD_SOCKET 32u     /* socket >= max_sockets: the packet is not taken (status 0) */
+
+/* State for n_hosts source hosts on the plan's device and stream, or, with
+ * plan == NULL, a host-only instance: every array argument of the other calls
+ * is then a HOST pointer and the calls complete before they return.  Both
+ * forms run the same per-host step.  bw_up_bytes_per_s: HOST pointer, each
+ * host's requested bandwidth_up in bits / 8.  qdisc: SRT_QDISC_*, one for all
+ * hosts.  max_sockets: sockets a host may name.  queue_cap (< 2^31 - 2):
+ * packets a host may hold unresolved in its socket queues across calls.
+ * Memory of the instance, in bytes:
+ *   n_hosts * (96 + queue_cap * 32 + max_sockets * 12)
+ * (state record; ring of carried-over packets; per socket an 8-byte head /
+ * tail cursor and a 4-byte slot of the qdisc's socket queue), plus 4 bytes a
+ * packet of the largest batch seen (the per-socket links).  Buckets start
+ * full, last refill at 0.  Destroy the instance before its plan. */
+srt_status srt_outbound_create(srt_plan *plan, uint32_t n_hosts, const uint64_t *bw_up_bytes_per_s, uint32_t qdisc,
+                               uint32_t max_sockets, uint32_t queue_cap, srt_outbound **out, srt_err *err);
+/* One scheduling window.  d_pkts: n_pkts (< 2^31) packets grouped by source
+ * host, d_host_ptr[h] .. d_host_ptr[h+1] being host h's (n_hosts + 1 entries),
+ * each host's in arrival order with nondecreasing ready_ns inside [previous
+ * call's until_ns, until_ns).  Every arrival is pushed at its ready_ns and
+ * every forward task with a time < until_ns runs.  An earlier arrival is
+ * flagged (TIME_REGRESSION); an arrival at or after until_ns is NOT taken
+ * (status 0, not pending, AFTER_UNTIL) and must be fed again with its window,
+ * as must a packet with a bad socket once corrected.
+ * Outputs, per batch packet: d_status (0: not taken, or still in a socket
+ * queue and counted pending; INTERFACE_SENT | RELAY_CACHED: the relay's cached
+ * packet at until_ns; INTERFACE_SENT | RELAY_FORWARDED, plus RELAY_CACHED if it
+ * was ever held back: forwarded), d_send_ns (the forward time, UINT64_MAX
+ * unless forwarded) and d_send_rank (the packet's position in its host's whole
+ * send sequence since create: the counter is per host, continues across calls
+ * and is advanced only by non-local forwarded packets; UINT64_MAX for local or
+ * unforwarded packets).  Sorting a round's forwarded non-local packets, late
+ * ones included, by (source host, send_rank) gives the send order
+ * srt_packet_batch needs.  A packet still in the stage stays there under the
+ * sequence number *seq_base + batch index (seq_base: host pointer, may be
+ * NULL).  Packets of earlier calls that are forwarded in this one are appended
+ * to d_late (late_cap records, any order) and counted in *d_late_count (written
+ * by the call; beyond late_cap: SRT_OUTBOUND_LATE_OVERFLOW).
+ * Asynchronous on the plan's stream, like srt_inbound_run. */
+srt_status srt_outbound_run(srt_outbound *ob, const srt_out_pkt *d_pkts, const uint32_t *d_host_ptr, uint64_t n_pkts,
+                            uint64_t until_ns, uint64_t bootstrap_end_ns, uint32_t *d_status, uint64_t *d_send_ns,
+                            uint64_t *d_send_rank, srt_outbound_late *d_late, uint32_t late_cap,
+                            uint32_t *d_late_count, uint64_t *seq_base, srt_err *err);
+/* Synchronises the stream.  *flags (may be NULL): the SRT_OUTBOUND_* conditions
+ * met since the last status call (then cleared); *n_pending (may be NULL):
+ * packets still in the stage.  SRT_ERR_INVALID when a flag is set (a ring
+ * overflow never writes out of bounds: the host is marked in its state and
+ * only its results are invalid), else SRT_OK. */
+srt_status srt_outbound_status(srt_outbound *ob, uint32_t *flags, uint64_t *n_pending, srt_err *err);
+/* Synchronises and copies every host's state to out[n_hosts] (HOST pointer). */
+srt_status srt_outbound_state(srt_outbound *ob, srt_outbound_host_state *out, srt_err *err);
+void srt_outbound_destroy(srt_outbound *ob);
 
 /* ---------------------------------------------------- IP assignment (a10) */
 /* IpAssignment<u32> (src/main/network/graph/mod.rs:352-420): IPv4 address ->

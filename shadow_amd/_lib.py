@@ -26,9 +26,15 @@ SRT_OPT_SAME_DEVICE = 1  # srt_opts.flags: every n_gpus rank on `device` (tests)
 PDS_NONE, PDS_INET_SENT, PDS_INET_DROPPED = 0, 1 << 8, 1 << 9
 PDS_ROUTER_ENQUEUED, PDS_ROUTER_DEQUEUED, PDS_ROUTER_DROPPED = 1 << 10, 1 << 11, 1 << 12
 PDS_RELAY_CACHED, PDS_RELAY_FORWARDED = 1 << 21, 1 << 22
+PDS_SND_INTERFACE_SENT = 1 << 7
 # srt_inbound_status flags
 INBOUND_RING_OVERFLOW, INBOUND_LATE_OVERFLOW, INBOUND_TIME_REGRESSION, INBOUND_OVERSIZE = 1, 2, 4, 8
 INBOUND_AFTER_UNTIL = 16
+# srt_outbound_create qdiscs, srt_out_pkt flags, srt_outbound_status flags
+QDISC_FIFO, QDISC_RR = 0, 1
+OUT_LOCAL = 1
+OUTBOUND_RING_OVERFLOW, OUTBOUND_LATE_OVERFLOW, OUTBOUND_TIME_REGRESSION, OUTBOUND_OVERSIZE = 1, 2, 4, 8
+OUTBOUND_AFTER_UNTIL, OUTBOUND_BAD_SOCKET = 16, 32
 
 
 class SrtErr(C.Structure):
@@ -78,6 +84,22 @@ class SrtInboundHostState(C.Structure):
                 ("previous_drop_count", C.c_uint64), ("queue_len", C.c_uint64), ("bytes_stored", C.c_uint64),
                 ("task_ns", C.c_uint64), ("tasks_scheduled", C.c_uint64), ("mode", C.c_uint32),
                 ("cached", C.c_uint32), ("overflow", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
+class SrtOutPkt(C.Structure):
+    _fields_ = [("ready_ns", C.c_uint64), ("priority", C.c_uint64), ("total_size", C.c_uint32),
+                ("socket", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SrtOutboundLate(C.Structure):
+    _fields_ = [("seq", C.c_uint64), ("send_ns", C.c_uint64), ("send_rank", C.c_uint64), ("status", C.c_uint32),
+                ("src_host", C.c_uint32)]
+
+
+class SrtOutboundHostState(C.Structure):
+    _fields_ = [("balance", C.c_uint64), ("last_refill_ns", C.c_uint64), ("task_ns", C.c_uint64),
+                ("tasks_scheduled", C.c_uint64), ("sent_total", C.c_uint64), ("queue_len", C.c_uint64),
+                ("cached", C.c_uint32), ("overflow", C.c_uint32)]
 
 
 class SrtError(RuntimeError):
@@ -137,6 +159,13 @@ SIGNATURES = {
     "srt_inbound_state": (C.c_int, [_vp, C.POINTER(SrtInboundHostState), _errp]),
     "srt_inbound_control_law": (C.c_int, [_vp, _u64p, C.c_uint64, C.c_int, _u64p, _errp]),
     "srt_inbound_destroy": (None, [_vp]),
+    "srt_outbound_create": (C.c_int, [_vp, C.c_uint32, _u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp),
+                                      _errp]),
+    "srt_outbound_run": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp,
+                                   C.c_uint32, _vp, _u64p, _errp]),
+    "srt_outbound_status": (C.c_int, [_vp, _u32p, _u64p, _errp]),
+    "srt_outbound_state": (C.c_int, [_vp, C.POINTER(SrtOutboundHostState), _errp]),
+    "srt_outbound_destroy": (None, [_vp]),
     "srt_routing_info_build": (C.c_int, [C.POINTER(SrtCsr), _u32p, C.c_uint32, C.c_int, C.POINTER(SrtOpts),
                                          C.POINTER(_vp), _errp]),
     "srt_routing_info_from_plan": (C.c_int, [_vp, C.POINTER(_vp), _errp]),

@@ -3088,6 +3088,7 @@ hipError_t preload_packet();
 hipError_t preload_direct();
 hipError_t preload_events();
 hipError_t preload_inbound();
+hipError_t preload_outbound();
 hipError_t preload_kernels() {
     hipError_t e = preload_fw();
     if (e == hipSuccess) e = preload_loss();
@@ -3097,6 +3098,7 @@ hipError_t preload_kernels() {
     if (e == hipSuccess) e = preload_direct();
     if (e == hipSuccess) e = preload_events();
     if (e == hipSuccess) e = preload_inbound();
+    if (e == hipSuccess) e = preload_outbound();
     return e;
 }
 

@@ -31,20 +31,25 @@
 
 #include "../../include/srt.h"
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define INB_HD __host__ __device__ __forceinline__
-#else
-#define INB_HD inline
-#endif
+#include "srt_relay_common.h"
+
+#define INB_HD SRT_HD
 
 namespace inb {
 
-constexpr uint64_t NONE = ~0ull;            // Option::None of the reference's EmulatedTime options
+// the bucket and the saturating helpers are srt_relay_common.h's, shared with the outbound step
+using relay::add_pending;
+using relay::MTU;
+using relay::NONE;
+using relay::raise;
+using relay::REFILL_NS;
+using relay::sat_add;
+using relay::sat_mul;
+using relay::sat_sub;
+using relay::take_slot;
+
 constexpr uint64_t TARGET_NS = 10000000;    // codel_queue.rs:23
 constexpr uint64_t INTERVAL_NS = 100000000;  // codel_queue.rs:28
-constexpr uint64_t MTU = 1500;              // CONFIG_MTU (definitions.h:124)
-constexpr uint64_t REFILL_NS = 1000000;     // relay/mod.rs:278
 constexpr uint32_t LAW_TABLE = 1024;        // control-law increments kept in a table
 
 constexpr uint32_t F_RING_OVERFLOW = 1, F_LATE_OVERFLOW = 2, F_TIME_REGRESSION = 4, F_OVERSIZE = 8,
@@ -101,37 +106,6 @@ struct Ctx {
     uint32_t n_hosts, ring_cap, late_cap, n_pkts;
     uint32_t win_cap, pad;  // records a wave may hold in LDS (device)
 };
-
-INB_HD uint64_t sat_add(uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; }
-INB_HD uint64_t sat_sub(uint64_t a, uint64_t b) { return a > b ? a - b : 0; }
-INB_HD uint64_t sat_mul(uint64_t a, uint64_t b) {
-    uint64_t r;
-    return __builtin_mul_overflow(a, b, &r) ? ~0ull : r;
-}
-
-INB_HD void raise(uint32_t *flags, uint32_t bit) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicOr(flags, bit);
-#else
-    *flags |= bit;
-#endif
-}
-
-INB_HD void add_pending(unsigned long long *total, unsigned long long n) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (n) atomicAdd(total, n);
-#else
-    *total += n;
-#endif
-}
-
-INB_HD uint32_t take_slot(uint32_t *count) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return atomicAdd(count, 1u);
-#else
-    return (*count)++;
-#endif
-}
 
 // apply_control_law's increment (codel_queue.rs:288-296) in f64: the value the
 // table holds for small counts and the path beyond it
@@ -280,23 +254,7 @@ struct Run {
 
     // TokenBucket::conforming_remove_inner (token_bucket.rs:75-157); false: *wait
     INB_HD bool conforming_remove(uint64_t dec, uint64_t now, uint64_t &wait) {
-        uint64_t span = sat_sub(now, s.last_refill);
-        if (span >= REFILL_NS) {  // lazy_refill
-            const uint64_t n = span / REFILL_NS;
-            const uint64_t b = sat_add(s.balance, sat_mul(s.refill, n));
-            s.balance = b < s.capacity ? b : s.capacity;
-            s.last_refill = sat_add(s.last_refill, sat_mul(REFILL_NS, n));
-            span = sat_sub(now, s.last_refill);
-        }
-        const uint64_t next_refill = REFILL_NS - span;
-        if (s.balance >= dec) {
-            s.balance -= dec;
-            return true;
-        }
-        const uint64_t need = dec - s.balance;
-        const uint64_t refills = need / s.refill + (need % s.refill ? 1 : 0);
-        wait = refills <= 1 ? next_refill : sat_add(next_refill, sat_mul(REFILL_NS, refills - 1));
-        return false;
+        return relay::bucket_remove(s.balance, s.last_refill, s.refill, s.capacity, dec, now, wait);
     }
 
     // Relay::forward_until_blocked (relay/mod.rs:200-272) at the task's time

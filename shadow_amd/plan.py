@@ -105,7 +105,7 @@ class RoutingPlan:
         return self._h
 
     def close(self):
-        for r in list(getattr(self, "_routers", ())):  # InboundRouter objects bound to this plan
+        for r in list(getattr(self, "_routers", ())):  # InboundRouter / OutboundRelay objects bound to this plan
             r.close()
         if self._h:
             _lib.lib().srt_plan_destroy(self._h)
@@ -218,6 +218,24 @@ def _close_live_routers():
             pass
 
 
+def _bind_to_plan(obj, plan):
+    """the plan closes `obj` before itself (it runs on the plan's stream); an
+    object left open (a caller that raised) is closed while the HIP runtime is
+    still up, not by a finaliser during interpreter shutdown"""
+    import weakref
+
+    if not hasattr(plan, "_routers"):
+        plan._routers = weakref.WeakSet()
+    plan._routers.add(obj)
+    global _live_routers
+    if _live_routers is None:
+        import atexit
+
+        _live_routers = weakref.WeakSet()
+        atexit.register(_close_live_routers)
+    _live_routers.add(obj)
+
+
 class InboundRouter:
     """srt_inbound: every destination host's CoDel queue and download token
     bucket (router/codel_queue.rs, relay/mod.rs, relay/token_bucket.rs) behind
@@ -326,3 +344,129 @@ class InboundRouter:
             self.close()
         except Exception:
             pass
+
+
+OUT_PKT_DTYPE = np.dtype([("ready_ns", "<u8"), ("priority", "<u8"), ("total_size", "<u4"), ("socket", "<u4"),
+                          ("flags", "<u4"), ("reserved", "<u4")])
+OUTBOUND_STATE_DTYPE = np.dtype([(k, "<u8") for k in (
+    "balance", "last_refill_ns", "task_ns", "tasks_scheduled", "sent_total", "queue_len")] + [
+        (k, "<u4") for k in ("cached", "overflow")])
+OUTBOUND_LATE_DTYPE = np.dtype([("seq", "<u8"), ("send_ns", "<u8"), ("send_rank", "<u8"), ("status", "<u4"),
+                                ("src_host", "<u4")])
+
+
+class OutboundRelay:
+    """srt_outbound: every source host's interface qdisc over its sockets and
+    its upload token bucket (network_interface.c, network_queuing_disciplines.c,
+    relay/mod.rs, relay/token_bucket.rs) in front of the send decision, one
+    call per scheduling window.
+
+    Bound to a RoutingPlan (arrays are torch CUDA tensors of its device, the
+    call is asynchronous on its stream; closing the plan closes its relays), or
+    host-only with plan=None (arrays are numpy arrays, the same per-host step
+    on the CPU)."""
+
+    def __init__(self, plan: Optional[RoutingPlan], bw_up_bytes_per_s, qdisc: int, max_sockets: int, queue_cap: int):
+        self.plan = plan
+        bw = np.ascontiguousarray(bw_up_bytes_per_s, np.uint64)
+        self.n_hosts = len(bw)
+        self._h = C.c_void_p()
+        if plan is not None:
+            _bind_to_plan(self, plan)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_outbound_create(plan.handle if plan is not None else None, self.n_hosts,
+                                                  bw.ctypes.data_as(C.POINTER(C.c_uint64)), int(qdisc),
+                                                  int(max_sockets), int(queue_cap), C.byref(self._h),
+                                                  C.byref(err)), err)
+
+    _ptr = staticmethod(InboundRouter._ptr)
+
+    def run(self, pkts, host_ptr, until_ns: int, bootstrap_end_ns: int, status, send_ns, send_rank, late=None,
+            late_count=None) -> int:
+        """srt_outbound_run.  pkts: a uint8 view of 32-byte srt_out_pkt records
+        (OUT_PKT_DTYPE) grouped by source host, host_ptr int32/uint32
+        [n_hosts+1]; outputs status int32/uint32, send_ns and send_rank
+        int64/uint64, all [n_pkts]; late: a uint8 buffer of 32-byte
+        srt_outbound_late records (OUTBOUND_LATE_DTYPE) with late_count a
+        1-element int32/uint32.  Returns the batch's sequence base.  Device
+        form: enqueue only (status() synchronises)."""
+        n_pkts = int(status.numel() if hasattr(status, "numel") else status.size)
+        late_cap = 0
+        if late is not None:
+            late_cap = int(late.numel() * late.element_size() if hasattr(late, "numel") else late.nbytes) // 32
+        cur = ps = None
+        if self.plan is not None:
+            import torch
+
+            ps = torch.cuda.ExternalStream(self.plan.stream_ptr(), device=status.device)
+            cur = torch.cuda.current_stream(status.device)
+            ps.wait_stream(cur)
+        base = C.c_uint64()
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_outbound_run(
+            self._h, self._ptr(pkts), self._ptr(host_ptr), n_pkts, int(until_ns), int(bootstrap_end_ns),
+            self._ptr(status), self._ptr(send_ns), self._ptr(send_rank), self._ptr(late), late_cap,
+            self._ptr(late_count), C.byref(base), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)  # torch-side consumers see the outputs (device-side ordering)
+        return base.value
+
+    def status(self, check: bool = True):
+        """srt_outbound_status: synchronises; (flags, packets still pending).
+        check=True raises SrtError when a flag is set."""
+        flags, pending = C.c_uint32(), C.c_uint64()
+        err = _lib.SrtErr()
+        rc = _lib.lib().srt_outbound_status(self._h, C.byref(flags), C.byref(pending), C.byref(err))
+        if check or (rc != _lib.SRT_OK and not flags.value):
+            _lib.check(rc, err)
+        return flags.value, pending.value
+
+    def state(self) -> np.ndarray:
+        """Every host's state (OUTBOUND_STATE_DTYPE record array)."""
+        out = np.zeros(self.n_hosts, OUTBOUND_STATE_DTYPE)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_outbound_state(
+            self._h, out.ctypes.data_as(C.POINTER(_lib.SrtOutboundHostState)), C.byref(err)), err)
+        return out
+
+    def close(self):
+        if self._h:
+            _lib.lib().srt_outbound_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def outbound_send_order(host_ptr, send_rank, late_src_host=None, late_send_rank=None):
+    """The grouped send order srt_packet_batch needs, from a round's
+    OutboundRelay.run outputs, with torch ops on the tensors' device.
+
+    host_ptr [n_hosts+1] (host_ptr[-1] == n_pkts) and send_rank int64 [n_pkts]
+    (-1 == UINT64_MAX: local or not forwarded) describe the batch; late_src_host / late_send_rank (the
+    first late_count records' fields) the packets of earlier calls forwarded in
+    this one.  Returns (order, send_host_ptr): order int64 [n_sent] names the
+    forwarded non-local packets grouped by source host, each host's by rank --
+    a value i < n_pkts is batch packet i, a value n_pkts + k is late record k
+    -- and send_host_ptr int32 [n_hosts+1] is the grouping of order."""
+    import torch
+
+    n_hosts = host_ptr.numel() - 1
+    n_pkts = send_rank.numel()
+    hp = host_ptr.to(torch.int64)
+    host = torch.repeat_interleave(torch.arange(n_hosts, device=hp.device), hp[1:] - hp[:-1], output_size=n_pkts)
+    rank = send_rank.to(torch.int64)
+    if late_src_host is not None and late_src_host.numel():
+        host = torch.cat([host, late_src_host.to(torch.int64)])
+        rank = torch.cat([rank, late_send_rank.to(torch.int64)])
+    sent = torch.nonzero(rank >= 0).flatten()
+    # two stable sorts: by rank, then by host (ranks are below 2^63, hosts below 2^32)
+    o = sent[torch.sort(rank[sent], stable=True).indices]
+    o = o[torch.sort(host[o], stable=True).indices]
+    counts = torch.bincount(host[o], minlength=n_hosts)
+    ptr = torch.zeros(n_hosts + 1, dtype=torch.int64, device=hp.device)
+    ptr[1:] = torch.cumsum(counts, 0)
+    return o, ptr.to(torch.int32)
