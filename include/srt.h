@@ -544,7 +544,8 @@ srt_status srt_outbound_create(srt_plan *plan, uint32_t n_hosts, const uint64_t 
  * and is advanced only by non-local forwarded packets; UINT64_MAX for local or
  * unforwarded packets).  Sorting a round's forwarded non-local packets, late
  * ones included, by (source host, send_rank) gives the send order
- * srt_packet_batch needs.  A packet still in the stage stays there under the
+ * srt_packet_batch needs (srt_sendbatch_run below builds that batch on the
+ * device, without a sort).  A packet still in the stage stays there under the
  * sequence number *seq_base + batch index (seq_base: host pointer, may be
  * NULL).  Packets of earlier calls that are forwarded in this one are appended
  * to d_late (late_cap records, any order) and counted in *d_late_count (written
@@ -563,6 +564,84 @@ srt_status srt_outbound_status(srt_outbound *ob, uint32_t *flags, uint64_t *n_pe
 /* Synchronises and copies every host's state to out[n_hosts] (HOST pointer). */
 srt_status srt_outbound_state(srt_outbound *ob, srt_outbound_host_state *out, srt_err *err);
 void srt_outbound_destroy(srt_outbound *ob);
+
+/* ------------------------------------------------------ send-batch gather */
+/* From srt_outbound_run's results to srt_packet_batch's input, on the device:
+ * the forwarded non-local packets of one outbound call, late ones included,
+ * as srt_pkt records grouped by source host, each host's in send_rank order,
+ * with t_ns = send_ns.  No sort is involved: within one srt_outbound_run call
+ * every rank a host hands out comes from its one counter, so a host's ranks of
+ * the call are one contiguous run [first, first + count) and a packet's place
+ * is host_base[h] + (rank - first[h]): a count and a minimum per host, a scan
+ * over the hosts, a scatter.  The arrays of ONE outbound call go in together;
+ * mixing calls breaks the run and is flagged (RANK_GAP).
+ * ABI: additive to version 4; detect the stage by its symbols. */
+
+/* what srt_pkt needs beyond what the outbound stage returns, 16 bytes */
+typedef struct { uint32_t src_row, dst_row, payload_size, user; } srt_send_meta;
+typedef struct srt_sendbatch srt_sendbatch;
+
+#define SRT_SENDBATCH_OUT_OVERFLOW 1u /* more sent packets than out_cap: nothing past out_cap written */
+#define SRT_SENDBATCH_RANK_GAP     2u /* a host's ranks are not one contiguous run (arrays of different calls mixed) */
+#define SRT_SENDBATCH_LOG_OVERRUN  4u /* a late packet's seq is older than the log holds */
+#define SRT_SENDBATCH_BAD_HOST     8u /* a late record's src_host >= n_hosts: skipped */
+
+/* An instance for n_hosts source hosts on the plan's device and stream, or,
+ * with plan == NULL, host-only: every array argument of srt_sendbatch_run is
+ * then a HOST pointer and the calls complete before they return.  Both forms
+ * run the same step.  The instance owns a log of log_cap srt_send_meta records
+ * (16 bytes each) and 12 bytes of scratch a host; nothing is allocated per
+ * call.  Destroy the instance before its plan. */
+srt_status srt_sendbatch_create(srt_plan *plan, uint32_t n_hosts, uint64_t log_cap,
+                                srt_sendbatch **out, srt_err *err);
+/* One gather, for the srt_outbound_run call just made: d_host_ptr, n_pkts
+ * (< 2^31), d_send_ns and d_send_rank are that call's arguments and outputs,
+ * seq_base the value it returned, d_late / late_cap (< 2^31) / d_late_count its
+ * late list, of which min(*d_late_count, late_cap) records are used (the count
+ * runs past the cap on overflow).  d_meta[i] belongs to batch packet i; `user`
+ * is opaque and comes back in d_out_user (typically the destination host
+ * srt_packet_events wants).
+ * The log keeps the meta of packets that stay in the outbound stage, addressed
+ * by seq % log_cap.  A batch packet without a rank (send_rank == UINT64_MAX:
+ * not forwarded in this call, or local) has its meta written at seq_base + i,
+ * provided n_pkts - i <= log_cap; a late packet's meta is read back from the
+ * log, and its seq is valid iff seq_base + n_pkts - seq <= log_cap, else the
+ * call is flagged LOG_OVERRUN and the record is emitted with rows 0, payload 0
+ * and user = UINT32_MAX.  The rule measures the distance from the END of this
+ * call's sequence range, so a slot it reads is never one this call writes: it
+ * does not depend on the order of the call's own writes.  Size log_cap to the
+ * packets fed while a packet may stay queued (queue_cap packets a host at
+ * most, over however many calls they take to drain).
+ * Outputs: d_out_host_ptr[0 .. n_hosts] is the grouping, [n_hosts] the number
+ * of sent packets; d_out_pkts[k] = {src_host, src_row, dst_row, payload_size,
+ * t_ns = send_ns} in send order; d_out_user and d_out_seq are parallel to it
+ * (seq_base + index for a batch packet, the late record's seq for a late one:
+ * the caller can carry anything else along by it).  src_row and dst_row are
+ * copied verbatim, so with addresses in them the same output is the srt_pkt_ip
+ * input of srt_packet_batch_ip.  At most out_cap records are written; with
+ * more sent packets the call is flagged OUT_OVERFLOW and every entry of
+ * d_out_host_ptr is held at out_cap, so that a consumer stays inside the
+ * arrays (srt_sendbatch_status still reports the true count).
+ * Every write is range-checked first (rank - first < count, position <
+ * out_cap, src_host < n_hosts): a flagged call never writes out of bounds.
+ * No host round trip is needed before the send decision: srt_packet_batch
+ * launches by hosts and reads packets only through its host_pkt_ptr, its n_pkts
+ * only sizes scratch, so the caller may pass out_cap there, with d_flags and
+ * d_deliver of out_cap entries.
+ * Asynchronous on the plan's stream: it never waits for the device. */
+srt_status srt_sendbatch_run(srt_sendbatch *sb, const uint32_t *d_host_ptr, uint64_t n_pkts,
+                             const srt_send_meta *d_meta, const uint64_t *d_send_ns,
+                             const uint64_t *d_send_rank, uint64_t seq_base,
+                             const srt_outbound_late *d_late, uint32_t late_cap,
+                             const uint32_t *d_late_count,
+                             srt_pkt *d_out_pkts, uint32_t *d_out_host_ptr, uint32_t *d_out_user,
+                             uint64_t *d_out_seq, uint64_t out_cap, srt_err *err);
+/* Synchronises the stream.  *flags (may be NULL): the SRT_SENDBATCH_*
+ * conditions met since the last status call (then cleared); *n_sent (may be
+ * NULL): the last call's sent packets.  SRT_ERR_INVALID, with a message that
+ * names every flag set, when any was; else SRT_OK. */
+srt_status srt_sendbatch_status(srt_sendbatch *sb, uint32_t *flags, uint64_t *n_sent, srt_err *err);
+void srt_sendbatch_destroy(srt_sendbatch *sb);
 
 /* ---------------------------------------------------- IP assignment (a10) */
 /* IpAssignment<u32> (src/main/network/graph/mod.rs:352-420): IPv4 address ->

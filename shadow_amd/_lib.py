@@ -35,6 +35,8 @@ QDISC_FIFO, QDISC_RR = 0, 1
 OUT_LOCAL = 1
 OUTBOUND_RING_OVERFLOW, OUTBOUND_LATE_OVERFLOW, OUTBOUND_TIME_REGRESSION, OUTBOUND_OVERSIZE = 1, 2, 4, 8
 OUTBOUND_AFTER_UNTIL, OUTBOUND_BAD_SOCKET = 16, 32
+# srt_sendbatch_status flags
+SENDBATCH_OUT_OVERFLOW, SENDBATCH_RANK_GAP, SENDBATCH_LOG_OVERRUN, SENDBATCH_BAD_HOST = 1, 2, 4, 8
 
 
 class SrtErr(C.Structure):
@@ -166,6 +168,11 @@ SIGNATURES = {
     "srt_outbound_status": (C.c_int, [_vp, _u32p, _u64p, _errp]),
     "srt_outbound_state": (C.c_int, [_vp, C.POINTER(SrtOutboundHostState), _errp]),
     "srt_outbound_destroy": (None, [_vp]),
+    "srt_sendbatch_create": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.POINTER(_vp), _errp]),
+    "srt_sendbatch_run": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp,
+                                    _vp, _vp, C.c_uint64, _errp]),
+    "srt_sendbatch_status": (C.c_int, [_vp, _u32p, _u64p, _errp]),
+    "srt_sendbatch_destroy": (None, [_vp]),
     "srt_routing_info_build": (C.c_int, [C.POINTER(SrtCsr), _u32p, C.c_uint32, C.c_int, C.POINTER(SrtOpts),
                                          C.POINTER(_vp), _errp]),
     "srt_routing_info_from_plan": (C.c_int, [_vp, C.POINTER(_vp), _errp]),

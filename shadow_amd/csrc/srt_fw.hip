@@ -3089,6 +3089,7 @@ hipError_t preload_direct();
 hipError_t preload_events();
 hipError_t preload_inbound();
 hipError_t preload_outbound();
+hipError_t preload_sendbatch();
 hipError_t preload_kernels() {
     hipError_t e = preload_fw();
     if (e == hipSuccess) e = preload_loss();
@@ -3099,6 +3100,7 @@ hipError_t preload_kernels() {
     if (e == hipSuccess) e = preload_events();
     if (e == hipSuccess) e = preload_inbound();
     if (e == hipSuccess) e = preload_outbound();
+    if (e == hipSuccess) e = preload_sendbatch();
     return e;
 }
 

@@ -441,6 +441,93 @@ class OutboundRelay:
             pass
 
 
+SEND_META_DTYPE = np.dtype([("src_row", "<u4"), ("dst_row", "<u4"), ("payload_size", "<u4"), ("user", "<u4")])
+SRT_PKT_DTYPE = np.dtype([("src_host", "<u4"), ("src_row", "<u4"), ("dst_row", "<u4"), ("payload_size", "<u4"),
+                          ("t_ns", "<u8")])
+
+
+class SendBatch:
+    """srt_sendbatch: one OutboundRelay.run call's results gathered into the
+    grouped srt_pkt batch the send decision takes -- per host a count and the
+    smallest rank, a scan over the hosts, a scatter; no sort.  The instance
+    keeps the log of log_cap srt_send_meta records (SEND_META_DTYPE) through
+    which packets that leave the relay in a later call get their rows back.
+
+    Bound to a RoutingPlan (arrays are torch CUDA tensors of its device, the
+    call is asynchronous on its stream; closing the plan closes it), or
+    host-only with plan=None (arrays are numpy arrays, the same step on the
+    CPU)."""
+
+    def __init__(self, plan: Optional[RoutingPlan], n_hosts: int, log_cap: int):
+        self.plan = plan
+        self.n_hosts = int(n_hosts)
+        self._h = C.c_void_p()
+        if plan is not None:
+            _bind_to_plan(self, plan)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_sendbatch_create(plan.handle if plan is not None else None, self.n_hosts,
+                                                   int(log_cap), C.byref(self._h), C.byref(err)), err)
+
+    _ptr = staticmethod(InboundRouter._ptr)
+
+    @staticmethod
+    def _nbytes(a):
+        if a is None:
+            return 0
+        return int(a.numel() * a.element_size() if hasattr(a, "numel") else a.nbytes)
+
+    def run(self, host_ptr, meta, send_ns, send_rank, seq_base: int, late, late_count, out_pkts, out_host_ptr,
+            out_user, out_seq):
+        """srt_sendbatch_run on the arrays of the OutboundRelay.run call just
+        made (host_ptr, send_ns, send_rank, its return value as seq_base, late,
+        late_count) and meta, a uint8 view of 16-byte srt_send_meta records,
+        one a batch packet.  Outputs: out_pkts, a uint8 buffer of out_cap
+        24-byte srt_pkt records, out_host_ptr int32/uint32 [n_hosts+1], out_user
+        int32/uint32 [out_cap] (its size is out_cap), out_seq int64/uint64
+        [out_cap].  Device form: enqueue only (status() synchronises)."""
+        n_pkts = int(send_rank.numel() if hasattr(send_rank, "numel") else send_rank.size)
+        late_cap = self._nbytes(late) // 32
+        out_cap = self._nbytes(out_user) // 4
+        if self._nbytes(out_pkts) < 24 * out_cap or self._nbytes(out_seq) < 8 * out_cap or \
+                self._nbytes(out_host_ptr) < 4 * (self.n_hosts + 1) or self._nbytes(meta) < 16 * n_pkts:
+            raise ValueError("SendBatch.run: an array is smaller than its record count")
+        cur = ps = None
+        if self.plan is not None:
+            import torch
+
+            ps = torch.cuda.ExternalStream(self.plan.stream_ptr(), device=out_host_ptr.device)
+            cur = torch.cuda.current_stream(out_host_ptr.device)
+            ps.wait_stream(cur)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_sendbatch_run(
+            self._h, self._ptr(host_ptr), n_pkts, self._ptr(meta), self._ptr(send_ns), self._ptr(send_rank),
+            int(seq_base), self._ptr(late), late_cap, self._ptr(late_count), self._ptr(out_pkts),
+            self._ptr(out_host_ptr), self._ptr(out_user), self._ptr(out_seq), out_cap, C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)  # torch-side consumers see the outputs (device-side ordering)
+
+    def status(self, check: bool = True):
+        """srt_sendbatch_status: synchronises; (flags, sent packets of the last
+        call).  check=True raises SrtError when a flag is set."""
+        flags, n_sent = C.c_uint32(), C.c_uint64()
+        err = _lib.SrtErr()
+        rc = _lib.lib().srt_sendbatch_status(self._h, C.byref(flags), C.byref(n_sent), C.byref(err))
+        if check or (rc != _lib.SRT_OK and not flags.value):
+            _lib.check(rc, err)
+        return flags.value, n_sent.value
+
+    def close(self):
+        if self._h:
+            _lib.lib().srt_sendbatch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def outbound_send_order(host_ptr, send_rank, late_src_host=None, late_send_rank=None):
     """The grouped send order srt_packet_batch needs, from a round's
     OutboundRelay.run outputs, with torch ops on the tensors' device.
