@@ -309,6 +309,96 @@ srt_status srt_packet_events(srt_plan *plan, const uint32_t *d_host_pkt_ptr, uin
  * returns SRT_OK; else SRT_OK. */
 srt_status srt_packet_events_status(srt_plan *plan, srt_err *err);
 
+/* -------------------------------------------------------- in-flight store */
+/* What joins the rounds to each other: Worker::send_packet clamps every
+ * deliver time to the round's end or later (worker.rs:396-400), and
+ * srt_inbound_run takes only the arrivals of its window, so the packets a
+ * round's event push numbered wait here, on the device, until a window reaches
+ * their deliver time.  The store keeps per packet its deliver time, source
+ * host, event id, destination host, total size and a 64-bit tag of the
+ * caller's (36 bytes), in one flat pool; a pop takes every stored packet with
+ * deliver < until_ns and hands them out as one window's batch in final order:
+ * grouped by destination host, each group in its event queue's pop order --
+ * deliver time, then source host id, then event id (core/work/event.rs:85-150),
+ * each compared as a full-width unsigned integer.  Event ids are unique per
+ * source host, so the key is a total order and the outputs are a pure function
+ * of the SET of stored packets; the order inside the pool is unspecified.
+ * ABI: additive to version 4; detect the stage by its symbols. */
+typedef struct srt_flight srt_flight;
+
+#define SRT_FLIGHT_POOL_OVERFLOW   1u  /* more packets in flight than pool_cap: the excess is NOT stored (counted) */
+#define SRT_FLIGHT_OUT_OVERFLOW    2u  /* more packets due than out_cap: the pop took NOTHING, the pool is unchanged */
+#define SRT_FLIGHT_BAD_HOST        4u  /* a sent packet's dst_host >= n_dst_hosts: not stored */
+#define SRT_FLIGHT_LATE_PUSH       8u  /* a pushed deliver time < the last pop's until_ns: stored, comes out at the next pop */
+#define SRT_FLIGHT_TIME_REGRESSION 16u /* a pop's until_ns < the previous pop's */
+
+/* A store for n_dst_hosts destination hosts and at most pool_cap (<= 2^31)
+ * packets in flight, on the plan's device and stream, or, with plan == NULL,
+ * host-only: every array argument of the other calls is then a HOST pointer
+ * and the calls complete before they return.  Both forms run the same step.
+ * Memory of the instance, in bytes, one allocation, nothing per call:
+ *   pool_cap * 108 + ceil(n_dst_hosts / 2) * 8 + 56
+ * (the pool twice, 2 * 36 bytes a packet: a pop compacts the survivors from one
+ * half into the other; 32 bytes a packet of staging, where a window's records
+ * lie grouped by destination before they are ordered, and 4 of its slot there;
+ * per destination a count; the state words).  Destroy the instance before its
+ * plan. */
+srt_status srt_flight_create(srt_plan *plan, uint32_t n_dst_hosts, uint64_t pool_cap,
+                             srt_flight **out, srt_err *err);
+
+/* After srt_packet_events of a round, its arguments and outputs as they are:
+ * d_host_pkt_ptr (n_src_hosts + 1 entries), n_pkts (< 2^31), d_flags,
+ * d_deliver, d_dst_host and d_event_id, plus every packet's total size
+ * (payload plus headers, what srt_inbound_run wants).  The store takes exactly
+ * the packets with flags[p] == SRT_PDS_INET_SENT, the test the event push
+ * applies; a packet's source host is the segment of host_pkt_ptr it lies in
+ * (host index order is HostId order).  d_tag (may be NULL) is opaque and comes
+ * back with the packet; without it the tag is the push's base + batch index,
+ * the base being the running count of all earlier pushes' n_pkts, returned in
+ * *tag_base (HOST pointer, may be NULL).  A destination >= n_dst_hosts is
+ * flagged (BAD_HOST) and skipped.  A packet for which the pool has no room is
+ * flagged (POOL_OVERFLOW) and counted in n_lost; nothing is written past the
+ * pool, and which packets of an overflowing push are the lost ones is
+ * unspecified.  A deliver time below the largest until_ns popped so far is
+ * flagged (LATE_PUSH); the packet is stored and leaves with the next pop.
+ * Asynchronous on the plan's stream: it never waits for the device. */
+srt_status srt_flight_push(srt_flight *fl, const uint32_t *d_host_pkt_ptr, uint32_t n_src_hosts, uint64_t n_pkts,
+                           const uint32_t *d_flags, const uint64_t *d_deliver, const uint32_t *d_dst_host,
+                           const uint64_t *d_event_id, const uint32_t *d_total_size,
+                           const uint64_t *d_tag /* may be NULL: tag_base + batch index */,
+                           uint64_t *tag_base /* host pointer, may be NULL, like seq_base elsewhere */, srt_err *err);
+
+/* One window: every stored packet with deliver < until_ns leaves the store.
+ * Outputs, out_cap entries each but d_w_dst_ptr (n_dst_hosts + 1): the group
+ * offsets d_w_dst_ptr (d_w_dst_ptr[n_dst_hosts] = the number popped), and in
+ * final order d_w_deliver, d_w_total_size, d_w_src_host, d_w_event_id, d_w_tag;
+ * d_w_order is the identity 0 .. n_popped, so that d_w_order, d_w_dst_ptr,
+ * d_w_deliver and d_w_total_size go into srt_inbound_run as they are with
+ * n_pkts = out_cap (the inbound stage bounds its walk by min(dst_ptr[n_hosts],
+ * n_pkts) on the device): no host round trip between the two calls.  Entries
+ * past the number popped are not written.  If more packets are due than
+ * out_cap the pop is void: nothing leaves, every d_w_dst_ptr entry is 0, the
+ * call is flagged (OUT_OVERFLOW) and srt_flight_status reports the true due
+ * count in n_popped, so that the caller can pop again with room; there is no
+ * partial window.  Survivors stay.  until_ns must not decrease (a smaller one
+ * is flagged TIME_REGRESSION and still takes what lies before it).  A
+ * destination group of any size comes out exact in the same call; one of more
+ * than 256 packets is ranked in quadratic time by one workgroup.
+ * Asynchronous on the plan's stream: it never waits for the device. */
+srt_status srt_flight_pop(srt_flight *fl, uint64_t until_ns,
+                          uint32_t *d_w_order, uint32_t *d_w_dst_ptr /* n_dst_hosts + 1 */,
+                          uint64_t *d_w_deliver, uint32_t *d_w_total_size, uint32_t *d_w_src_host,
+                          uint64_t *d_w_event_id, uint64_t *d_w_tag, uint64_t out_cap, srt_err *err);
+
+/* Synchronises the stream.  *flags (may be NULL): the SRT_FLIGHT_* conditions
+ * met since the last status call (then cleared); *n_popped: the last pop's due
+ * count, void or not; *n_stored: packets in the store; *n_lost: packets lost to
+ * POOL_OVERFLOW since create (all may be NULL).  SRT_ERR_INVALID, with a message
+ * that names every flag set, when any was; else SRT_OK. */
+srt_status srt_flight_status(srt_flight *fl, uint32_t *flags, uint64_t *n_popped, uint64_t *n_stored,
+                             uint64_t *n_lost, srt_err *err);
+void srt_flight_destroy(srt_flight *fl);
+
 /* --------------------------------------------------- inbound router stage */
 /* What the destination host does with the packet events srt_packet_events
  * ordered, batched over hosts: each packet event pushes its packet into the

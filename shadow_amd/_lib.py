@@ -37,6 +37,8 @@ OUTBOUND_RING_OVERFLOW, OUTBOUND_LATE_OVERFLOW, OUTBOUND_TIME_REGRESSION, OUTBOU
 OUTBOUND_AFTER_UNTIL, OUTBOUND_BAD_SOCKET = 16, 32
 # srt_sendbatch_status flags
 SENDBATCH_OUT_OVERFLOW, SENDBATCH_RANK_GAP, SENDBATCH_LOG_OVERRUN, SENDBATCH_BAD_HOST = 1, 2, 4, 8
+# srt_flight_status flags
+FLIGHT_POOL_OVERFLOW, FLIGHT_OUT_OVERFLOW, FLIGHT_BAD_HOST, FLIGHT_LATE_PUSH, FLIGHT_TIME_REGRESSION = 1, 2, 4, 8, 16
 
 
 class SrtErr(C.Structure):
@@ -173,6 +175,11 @@ SIGNATURES = {
                                     _vp, _vp, C.c_uint64, _errp]),
     "srt_sendbatch_status": (C.c_int, [_vp, _u32p, _u64p, _errp]),
     "srt_sendbatch_destroy": (None, [_vp]),
+    "srt_flight_create": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.POINTER(_vp), _errp]),
+    "srt_flight_push": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _u64p, _errp]),
+    "srt_flight_pop": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _errp]),
+    "srt_flight_status": (C.c_int, [_vp, _u32p, _u64p, _u64p, _u64p, _errp]),
+    "srt_flight_destroy": (None, [_vp]),
     "srt_routing_info_build": (C.c_int, [C.POINTER(SrtCsr), _u32p, C.c_uint32, C.c_int, C.POINTER(SrtOpts),
                                          C.POINTER(_vp), _errp]),
     "srt_routing_info_from_plan": (C.c_int, [_vp, C.POINTER(_vp), _errp]),

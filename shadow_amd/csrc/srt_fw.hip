@@ -3090,6 +3090,7 @@ hipError_t preload_events();
 hipError_t preload_inbound();
 hipError_t preload_outbound();
 hipError_t preload_sendbatch();
+hipError_t preload_flight();
 hipError_t preload_kernels() {
     hipError_t e = preload_fw();
     if (e == hipSuccess) e = preload_loss();
@@ -3101,6 +3102,7 @@ hipError_t preload_kernels() {
     if (e == hipSuccess) e = preload_inbound();
     if (e == hipSuccess) e = preload_outbound();
     if (e == hipSuccess) e = preload_sendbatch();
+    if (e == hipSuccess) e = preload_flight();
     return e;
 }
 

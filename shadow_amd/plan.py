@@ -528,6 +528,108 @@ class SendBatch:
             pass
 
 
+class FlightStore:
+    """srt_flight: the packets a round's send decision marked SENT, kept until
+    the window their deliver time falls in.  push() takes a round's
+    srt_packet_events arrays as they are; pop() hands out every stored packet
+    with deliver < until_ns grouped by destination host, each group in its
+    event queue's pop order (deliver, source host, event id), as the arrays
+    InboundRouter.run takes.
+
+    Bound to a RoutingPlan (arrays are torch CUDA tensors of its device, the
+    calls are asynchronous on its stream; closing the plan closes it), or
+    host-only with plan=None (arrays are numpy arrays, the same step on the
+    CPU)."""
+
+    def __init__(self, plan: Optional[RoutingPlan], n_dst_hosts: int, pool_cap: int):
+        self.plan = plan
+        self.n_dst_hosts = int(n_dst_hosts)
+        self._h = C.c_void_p()
+        if plan is not None:
+            _bind_to_plan(self, plan)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_flight_create(plan.handle if plan is not None else None, self.n_dst_hosts,
+                                                int(pool_cap), C.byref(self._h), C.byref(err)), err)
+
+    _ptr = staticmethod(InboundRouter._ptr)
+    _nbytes = staticmethod(SendBatch._nbytes)
+
+    def _streams(self, a):
+        if self.plan is None:
+            return None, None
+        import torch
+
+        ps = torch.cuda.ExternalStream(self.plan.stream_ptr(), device=a.device)
+        cur = torch.cuda.current_stream(a.device)
+        ps.wait_stream(cur)
+        return cur, ps
+
+    def push(self, host_ptr, flags, deliver, dst_host, event_id, total_size, tag=None) -> int:
+        """srt_flight_push after packet_events of a round: host_ptr int32/uint32
+        [n_src_hosts+1], flags int32/uint32, deliver int64/uint64, dst_host
+        int32/uint32, event_id int64/uint64, total_size int32/uint32, tag
+        int64/uint64 or None, all [n_pkts].  Returns the push's tag base.
+        Device form: enqueue only (status() synchronises)."""
+        n_pkts = self._nbytes(flags) // 4
+        if self._nbytes(deliver) < 8 * n_pkts or self._nbytes(dst_host) < 4 * n_pkts or \
+                self._nbytes(event_id) < 8 * n_pkts or self._nbytes(total_size) < 4 * n_pkts or \
+                (tag is not None and self._nbytes(tag) < 8 * n_pkts) or self._nbytes(host_ptr) < 4:
+            raise ValueError("FlightStore.push: an array is smaller than its record count")
+        cur, ps = self._streams(host_ptr)
+        base = C.c_uint64()
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_flight_push(
+            self._h, self._ptr(host_ptr), self._nbytes(host_ptr) // 4 - 1, n_pkts, self._ptr(flags),
+            self._ptr(deliver), self._ptr(dst_host), self._ptr(event_id), self._ptr(total_size), self._ptr(tag),
+            C.byref(base), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)
+        return base.value
+
+    def pop(self, until_ns: int, w_order, w_dst_ptr, w_deliver, w_total_size, w_src_host, w_event_id, w_tag):
+        """srt_flight_pop: one window.  Outputs w_order int32/uint32 (its size is
+        out_cap), w_dst_ptr int32/uint32 [n_dst_hosts+1], w_deliver
+        int64/uint64, w_total_size and w_src_host int32/uint32, w_event_id and
+        w_tag int64/uint64, [out_cap] each.  Device form: enqueue only
+        (status() synchronises and tells how many were popped)."""
+        out_cap = self._nbytes(w_order) // 4
+        if self._nbytes(w_dst_ptr) < 4 * (self.n_dst_hosts + 1) or self._nbytes(w_deliver) < 8 * out_cap or \
+                self._nbytes(w_total_size) < 4 * out_cap or self._nbytes(w_src_host) < 4 * out_cap or \
+                self._nbytes(w_event_id) < 8 * out_cap or self._nbytes(w_tag) < 8 * out_cap:
+            raise ValueError("FlightStore.pop: an array is smaller than its record count")
+        cur, ps = self._streams(w_dst_ptr)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_flight_pop(
+            self._h, int(until_ns), self._ptr(w_order), self._ptr(w_dst_ptr), self._ptr(w_deliver),
+            self._ptr(w_total_size), self._ptr(w_src_host), self._ptr(w_event_id), self._ptr(w_tag), out_cap,
+            C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)  # torch-side consumers see the outputs (device-side ordering)
+
+    def status(self, check: bool = True):
+        """srt_flight_status: synchronises; (flags, due count of the last pop,
+        packets stored, packets lost since create).  check=True raises SrtError
+        when a flag is set."""
+        flags, popped, stored, lost = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        err = _lib.SrtErr()
+        rc = _lib.lib().srt_flight_status(self._h, C.byref(flags), C.byref(popped), C.byref(stored), C.byref(lost),
+                                          C.byref(err))
+        if check or (rc != _lib.SRT_OK and not flags.value):
+            _lib.check(rc, err)
+        return flags.value, popped.value, stored.value, lost.value
+
+    def close(self):
+        if self._h:
+            _lib.lib().srt_flight_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def outbound_send_order(host_ptr, send_rank, late_src_host=None, late_send_rank=None):
     """The grouped send order srt_packet_batch needs, from a round's
     OutboundRelay.run outputs, with torch ops on the tensors' device.
