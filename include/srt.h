@@ -245,8 +245,9 @@ typedef struct {
 } srt_pkt;
 
 /* PacketDeliveryStatusFlags (src/main/routing/packet.minimal.h:24-36): the send
- * decision's two, the inbound router stage's five and the interface's one
- * (PDS_SND_INTERFACE_SENT, packet.minimal.h:21) of the outbound relay stage */
+ * decision's two, the inbound router stage's five, the interface's one
+ * (PDS_SND_INTERFACE_SENT, packet.minimal.h:21) of the outbound relay stage
+ * and its two of the receive stage (packet.minimal.h:27-28) */
 enum {
     SRT_PDS_NONE = 0,
     SRT_PDS_SND_INTERFACE_SENT = 1u << 7,
@@ -255,6 +256,8 @@ enum {
     SRT_PDS_ROUTER_ENQUEUED = 1u << 10,
     SRT_PDS_ROUTER_DEQUEUED = 1u << 11,
     SRT_PDS_ROUTER_DROPPED = 1u << 12,
+    SRT_PDS_RCV_INTERFACE_RECEIVED = 1u << 13,
+    SRT_PDS_RCV_INTERFACE_DROPPED = 1u << 14,
     SRT_PDS_RELAY_CACHED = 1u << 21,
     SRT_PDS_RELAY_FORWARDED = 1u << 22
 };
@@ -416,8 +419,9 @@ void srt_flight_destroy(srt_flight *fl);
  * times, the packet sizes and each host's download bandwidth.
  * OUT OF SCOPE: the CPU-delay model that reschedules events (host.rs:820-848),
  * the loopback relay (is_local is always false here; the outbound relay is the
- * srt_outbound stage below), and anything the interface does after it receives
- * the packet.
+ * srt_outbound stage below), and what the socket does with the packet: the
+ * interface's receive side up to the socket hand-off is the srt_deliver stage
+ * below.
  * ABI: additive to version 4; detect the stage by its symbols. */
 typedef struct srt_inbound srt_inbound;
 
@@ -511,6 +515,175 @@ srt_status srt_inbound_control_law(srt_inbound *ib, const uint64_t *counts, uint
                                    uint64_t *increments, srt_err *err);
 void srt_inbound_destroy(srt_inbound *ib);
 
+/* ----------------------------------------------- interface receive stage */
+/* What the destination host's interface does with the packets the inbound
+ * router forwarded, batched over hosts: networkinterface_push
+ * (host/network/network_interface.c:140-202, called from
+ * Relay::forward_until_blocked, network/relay/mod.rs:260-270) marks the packet
+ * RCV_INTERFACE_RECEIVED, looks its socket up in the host's associations --
+ * the specific key (protocol, destination port, source ip, source port) first,
+ * then the wildcard (protocol, destination port, 0, 0) -- and hands the packet
+ * to that socket, or marks it RCV_INTERFACE_DROPPED.  One call takes ONE
+ * srt_inbound_run call's results (per-packet status / forward_ns in window
+ * order, and the late list) and returns the per-host delivery list: exactly
+ * the packets with RELAY_FORWARDED, grouped by destination host, each host's
+ * in the order its interface receives them, which is the relay's forward order
+ * and the CoDel queue's FIFO order -- the host's late packets by ascending seq,
+ * then its batch packets by ascending position in the window -- each with its
+ * socket.  forward_ns is nondecreasing along every host's list for results of
+ * a correct inbound call (an invariant, not a sort key).  Windows are taken in
+ * final order (order[] the identity, as srt_flight_pop emits them), so the
+ * stage needs only d_dst_ptr and a packet's seq is seq_base + its position.
+ * The lookup uses the associations AS THEY STAND AT THE CALL, for late packets
+ * too: the reference looks up at push time, not at enqueue time.  Key fields
+ * are compared verbatim as integers (ports and addresses in network byte
+ * order).  A packet whose peer is 0:0 hits the wildcard key on the first probe,
+ * as in the reference, where the two keys are the same string.
+ * LIMIT: associations change only between calls.  The reference can associate
+ * or disassociate as a consequence of a delivery inside the window (a TCP
+ * close, say); a caller that disassociates a socket mid-window must treat the
+ * window's later deliveries to that socket as the lookup would, or split the
+ * window there.
+ * OUT OF SCOPE: pcap capture, the tracker's byte counts, what the socket does
+ * with the packet, the loopback relay, the CPU-delay model.
+ * ABI: additive to version 4; detect the stage by its symbols. */
+typedef struct srt_deliver srt_deliver;
+
+#define SRT_PROTO_TCP 1u /* ProtocolType PTCP (host/protocol.h:11) */
+#define SRT_PROTO_UDP 2u /* PUDP */
+
+/* what the lookup needs from a packet, 16 bytes; `user` is opaque and comes back */
+typedef struct {
+    uint32_t peer_ip_be;    /* the packet's source address */
+    uint16_t peer_port_be;  /* its source port */
+    uint16_t local_port_be; /* its destination port */
+    uint32_t protocol;      /* SRT_PROTO_*; any other value matches no association */
+    uint32_t user;
+} srt_rx_meta;
+
+/* one socket association of a host's interface, 20 bytes; the wildcard has peer 0:0 */
+typedef struct {
+    uint32_t host;
+    uint32_t protocol; /* SRT_PROTO_TCP or SRT_PROTO_UDP */
+    uint32_t peer_ip_be;
+    uint16_t local_port_be;
+    uint16_t peer_port_be;
+    uint32_t socket; /* < 2^31, the caller's name for the socket */
+} srt_assoc;
+
+#define SRT_DELIVER_OUT_OVERFLOW 1u /* more delivered packets than out_cap: nothing past out_cap written */
+#define SRT_DELIVER_LOG_OVERRUN  2u /* a late packet's seq is older than the log holds: a placeholder record */
+#define SRT_DELIVER_NOTE_OVERRUN 4u /* a tag the note ring no longer (or not yet) holds: a placeholder record */
+#define SRT_DELIVER_BAD_HOST     8u /* a late record's dst_host >= n_hosts: skipped */
+
+/* An instance for n_hosts destination hosts on the plan's device and stream,
+ * or, with plan == NULL, host-only: every array argument named d_ is then a
+ * HOST pointer and the calls complete before they return.  Both forms run the
+ * same step.  Memory of the instance, in bytes:
+ *   32 + n_hosts * 12 + note_cap * 16 + log_cap * 32 + slots * 16
+ * (the state words; per host three counts; the note ring of srt_rx_meta; the
+ * seq log of {tag, meta, valid}; the association table, slots being the
+ * smallest power of two >= max(table_slots_min, 2) that keeps the load at or
+ * below 1/2 -- it doubles when the associations outgrow it and never shrinks),
+ * on the device, plus the table once more in pinned host memory and the
+ * authoritative associations on the host.  Nothing is allocated per call; only
+ * the first run after the table has doubled waits for the stream and
+ * reallocates the device copy.  note_cap and log_cap are at most 2^31.
+ * Destroy the instance before its plan. */
+srt_status srt_deliver_create(srt_plan *plan, uint32_t n_hosts, uint32_t table_slots_min, uint64_t note_cap,
+                              uint64_t log_cap, srt_deliver **out, srt_err *err);
+
+/* networkinterface_associate / networkinterface_disassociate
+ * (network_interface.c:77-116) for a batch of n associations (HOST pointer),
+ * between calls of srt_deliver_run.  The authoritative table lives on the
+ * host; the device copy is rebuilt on the host and uploaded on the stream by
+ * the next srt_deliver_run, and only when the associations have changed since
+ * the last upload.  associate: a key that exists already -- in the table or
+ * twice in the batch -- a host >= n_hosts, a socket >= 2^31 or a protocol that
+ * is neither SRT_PROTO_TCP nor SRT_PROTO_UDP returns SRT_ERR_INVALID and
+ * changes NOTHING (the reference asserts there is no collision).
+ * disassociate: the socket field is ignored and a missing key is a no-op (the
+ * reference tolerates it, network_interface.c:106-112). */
+srt_status srt_deliver_associate(srt_deliver *dl, const srt_assoc *assoc, uint64_t n, srt_err *err);
+srt_status srt_deliver_disassociate(srt_deliver *dl, const srt_assoc *assoc, uint64_t n, srt_err *err);
+
+/* The lookup of the stage for n (host, meta) pairs against the same table, on
+ * the host (HOST pointers): sockets[k] is the socket, or UINT32_MAX.  For
+ * packets that never reach the inbound stage (SRT_OUT_LOCAL), and for tests. */
+srt_status srt_deliver_lookup(srt_deliver *dl, const uint32_t *hosts, const srt_rx_meta *meta, uint64_t n,
+                              uint32_t *sockets, srt_err *err);
+
+/* The table as the next run sees it (all may be NULL): associations, slots,
+ * the longest probe sequence of a stored key (1: every key in its home slot)
+ * and whether a chain runs past the table's end. */
+srt_status srt_deliver_table_stats(srt_deliver *dl, uint64_t *n_assoc, uint32_t *n_slots, uint32_t *max_probe,
+                                   uint32_t *wrapped, srt_err *err);
+
+/* After a round's srt_flight_push with d_tag == NULL: the round's metas, d_meta[i]
+ * for batch packet i, whose tag is tag_base + i (tag_base as the push returned
+ * it), go into the instance's ring at tag % note_cap.  tag_base must not lie
+ * below the previous note's end (SRT_ERR_INVALID).  A tag is readable iff tag <
+ * note_end && note_end - tag <= note_cap, note_end being the last note's
+ * tag_base + n_pkts: size note_cap to the packets pushed while a packet may be
+ * in flight or in its window.  n_pkts < 2^31.  Asynchronous on the plan's
+ * stream. */
+srt_status srt_deliver_note(srt_deliver *dl, const srt_rx_meta *d_meta, uint64_t n_pkts, uint64_t tag_base,
+                            srt_err *err);
+
+/* One delivery, for the srt_inbound_run call just made.  d_dst_ptr (n_hosts + 1
+ * entries) and d_tag are srt_flight_pop's d_w_dst_ptr and d_w_tag, d_status and
+ * d_forward_ns the inbound call's outputs, seq_base the value it returned,
+ * d_late / late_cap (< 2^31) / d_late_count its late list, of which
+ * min(*d_late_count, late_cap) records are used.  n_pkts (< 2^31) is the
+ * inbound call's n_pkts and may be the flight pop's out_cap: the walk is
+ * bounded by walked = min(d_dst_ptr[n_hosts], n_pkts) on the device, so there
+ * is no host round trip between pop, inbound and deliver.
+ * Outputs: d_out_host_ptr[0 .. n_hosts] is the grouping, [n_hosts] the number
+ * delivered; parallel to it in delivery order d_out_socket (UINT32_MAX: no
+ * socket), d_out_forward_ns, d_out_tag, d_out_user and d_out_status (the
+ * inbound status plus RCV_INTERFACE_RECEIVED, and RCV_INTERFACE_DROPPED when
+ * no socket took the packet), out_cap entries each.  With more delivered
+ * packets than out_cap the call is flagged OUT_OVERFLOW, nothing is written
+ * past out_cap and every d_out_host_ptr entry is held at out_cap at most, so
+ * that a consumer stays inside the arrays; the records of such a call, and
+ * which of the record flags below it raises, are unspecified, and
+ * srt_deliver_status still reports the true count.
+ * The seq log: a batch packet that stays in the inbound stage (ROUTER_ENQUEUED
+ * without RELAY_FORWARDED or ROUTER_DROPPED) has {tag, meta} written at
+ * (seq_base + i) % log_cap iff walked - i <= log_cap; a late packet's record is
+ * read back iff seq_base + n_pkts - seq <= log_cap, else the call is flagged
+ * LOG_OVERRUN.  Both are distances from the end of the call's range, so a slot
+ * read is never one this call writes.  Size log_cap to the sequence numbers
+ * handed out (n_pkts a call) while a packet may stay queued.
+ * Placeholders: a delivered packet whose meta cannot be had -- LOG_OVERRUN, or
+ * NOTE_OVERRUN, when its tag was not readable in the note ring at this call
+ * (batch) or at the call that logged it (late; both calls are flagged) -- is
+ * emitted in its place with socket = UINT32_MAX, user = UINT32_MAX, the inbound
+ * status unchanged (no RCV_ bit: not looked up) and tag = UINT64_MAX if the tag
+ * is lost too.  A late record with dst_host >= n_hosts is flagged BAD_HOST and
+ * skipped.  Every write is range-checked first: a flagged call never writes
+ * out of bounds.  A host's late run of any length comes out ordered in the
+ * same call; one of more than 256 records is ranked in quadratic time by one
+ * workgroup.
+ * Asynchronous on the plan's stream: it never waits for the device and reads
+ * nothing back. */
+srt_status srt_deliver_run(srt_deliver *dl, const uint32_t *d_dst_ptr, uint64_t n_pkts, const uint64_t *d_tag,
+                           const uint32_t *d_status, const uint64_t *d_forward_ns, uint64_t seq_base,
+                           const srt_inbound_late *d_late, uint32_t late_cap, const uint32_t *d_late_count,
+                           uint32_t *d_out_host_ptr, uint32_t *d_out_socket, uint64_t *d_out_forward_ns,
+                           uint64_t *d_out_tag, uint32_t *d_out_user, uint32_t *d_out_status, uint64_t out_cap,
+                           srt_err *err);
+/* Synchronises the stream.  *flags (may be NULL): the SRT_DELIVER_* conditions
+ * met since the last status call (then cleared); *n_delivered: the last run's
+ * delivered packets; *n_no_socket: those of them (written) that no socket took
+ * (both may be NULL; the device form sums the hosts' counts here, with one
+ * launch, so that no kernel of a run adds to a call-wide counter).
+ * SRT_ERR_INVALID, with a message that names every flag set, when any was;
+ * else SRT_OK. */
+srt_status srt_deliver_status(srt_deliver *dl, uint32_t *flags, uint64_t *n_delivered, uint64_t *n_no_socket,
+                              srt_err *err);
+void srt_deliver_destroy(srt_deliver *dl);
+
 /* --------------------------------------------------- outbound relay stage */
 /* What the source host does before Worker::send_packet, batched over hosts:
  * the step that produces srt_pkt.t_ns and the per-host send order
@@ -551,8 +724,9 @@ void srt_inbound_destroy(srt_inbound *ib);
  * arrival list (ready_ns, socket, priority, size, local flag), the qdisc and
  * bandwidth_up.
  * OUT OF SCOPE: how sockets produce packets (TCP/UDP buffers, retransmission),
- * the loopback relay, the CPU-delay model that reschedules events, and what the
- * interface does with a local packet pushed back into it.
+ * the loopback relay and the CPU-delay model that reschedules events.  A local
+ * packet pushed back into the interface is received as srt_deliver_run
+ * receives a forwarded one: srt_deliver_lookup resolves its socket.
  * ABI: additive to version 4; detect the stage by its symbols. */
 typedef struct srt_outbound srt_outbound;
 

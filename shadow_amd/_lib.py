@@ -27,6 +27,7 @@ PDS_NONE, PDS_INET_SENT, PDS_INET_DROPPED = 0, 1 << 8, 1 << 9
 PDS_ROUTER_ENQUEUED, PDS_ROUTER_DEQUEUED, PDS_ROUTER_DROPPED = 1 << 10, 1 << 11, 1 << 12
 PDS_RELAY_CACHED, PDS_RELAY_FORWARDED = 1 << 21, 1 << 22
 PDS_SND_INTERFACE_SENT = 1 << 7
+PDS_RCV_INTERFACE_RECEIVED, PDS_RCV_INTERFACE_DROPPED = 1 << 13, 1 << 14
 # srt_inbound_status flags
 INBOUND_RING_OVERFLOW, INBOUND_LATE_OVERFLOW, INBOUND_TIME_REGRESSION, INBOUND_OVERSIZE = 1, 2, 4, 8
 INBOUND_AFTER_UNTIL = 16
@@ -39,6 +40,9 @@ OUTBOUND_AFTER_UNTIL, OUTBOUND_BAD_SOCKET = 16, 32
 SENDBATCH_OUT_OVERFLOW, SENDBATCH_RANK_GAP, SENDBATCH_LOG_OVERRUN, SENDBATCH_BAD_HOST = 1, 2, 4, 8
 # srt_flight_status flags
 FLIGHT_POOL_OVERFLOW, FLIGHT_OUT_OVERFLOW, FLIGHT_BAD_HOST, FLIGHT_LATE_PUSH, FLIGHT_TIME_REGRESSION = 1, 2, 4, 8, 16
+# srt_assoc / srt_rx_meta protocols, srt_deliver_status flags
+PROTO_TCP, PROTO_UDP = 1, 2
+DELIVER_OUT_OVERFLOW, DELIVER_LOG_OVERRUN, DELIVER_NOTE_OVERRUN, DELIVER_BAD_HOST = 1, 2, 4, 8
 
 
 class SrtErr(C.Structure):
@@ -180,6 +184,16 @@ SIGNATURES = {
     "srt_flight_pop": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _errp]),
     "srt_flight_status": (C.c_int, [_vp, _u32p, _u64p, _u64p, _u64p, _errp]),
     "srt_flight_destroy": (None, [_vp]),
+    "srt_deliver_create": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(_vp), _errp]),
+    "srt_deliver_associate": (C.c_int, [_vp, _vp, C.c_uint64, _errp]),
+    "srt_deliver_disassociate": (C.c_int, [_vp, _vp, C.c_uint64, _errp]),
+    "srt_deliver_lookup": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _errp]),
+    "srt_deliver_table_stats": (C.c_int, [_vp, _u64p, _u32p, _u32p, _u32p, _errp]),
+    "srt_deliver_note": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _errp]),
+    "srt_deliver_run": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _vp, C.c_uint64, _errp]),
+    "srt_deliver_status": (C.c_int, [_vp, _u32p, _u64p, _u64p, _errp]),
+    "srt_deliver_destroy": (None, [_vp]),
     "srt_routing_info_build": (C.c_int, [C.POINTER(SrtCsr), _u32p, C.c_uint32, C.c_int, C.POINTER(SrtOpts),
                                          C.POINTER(_vp), _errp]),
     "srt_routing_info_from_plan": (C.c_int, [_vp, C.POINTER(_vp), _errp]),

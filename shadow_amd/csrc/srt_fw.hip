@@ -3091,6 +3091,7 @@ hipError_t preload_inbound();
 hipError_t preload_outbound();
 hipError_t preload_sendbatch();
 hipError_t preload_flight();
+hipError_t preload_deliver();
 hipError_t preload_kernels() {
     hipError_t e = preload_fw();
     if (e == hipSuccess) e = preload_loss();
@@ -3103,6 +3104,7 @@ hipError_t preload_kernels() {
     if (e == hipSuccess) e = preload_outbound();
     if (e == hipSuccess) e = preload_sendbatch();
     if (e == hipSuccess) e = preload_flight();
+    if (e == hipSuccess) e = preload_deliver();
     return e;
 }
 

@@ -12,8 +12,8 @@
 // the host-only instance alike.
 //
 // Out of scope: the CPU-delay model that reschedules events (host.rs:820-848),
-// the loopback relay (the outbound relay is srt_outbound.hip), and anything the
-// interface does after it receives the packet.
+// the loopback relay (the outbound relay is srt_outbound.hip), and what the
+// socket does with the packet (the interface's receive side is srt_deliver.hip).
 //
 // Device form, two launches a call on the plan's stream:
 //   (1) stage: one thread a position of order[]: the gathers behind it

@@ -630,6 +630,136 @@ class FlightStore:
             pass
 
 
+RX_META_DTYPE = np.dtype([("peer_ip_be", "<u4"), ("peer_port_be", "<u2"), ("local_port_be", "<u2"),
+                          ("protocol", "<u4"), ("user", "<u4")])
+ASSOC_DTYPE = np.dtype([("host", "<u4"), ("protocol", "<u4"), ("peer_ip_be", "<u4"), ("local_port_be", "<u2"),
+                        ("peer_port_be", "<u2"), ("socket", "<u4")])
+
+
+class DeliverStage:
+    """srt_deliver: the interface's receive stage behind InboundRouter.run
+    (networkinterface_push): the forwarded packets of one inbound call, late
+    ones included, grouped by destination host in the order the interface
+    receives them, each with the socket its host's associations give it at the
+    call.  associate() / disassociate() keep the associations (ASSOC_DTYPE
+    records, on the host); note() stores a round's RX_META_DTYPE records under
+    the flight tags of the round's push; run() delivers.
+
+    Bound to a RoutingPlan (arrays are torch CUDA tensors of its device, the
+    calls are asynchronous on its stream; closing the plan closes it), or
+    host-only with plan=None (arrays are numpy arrays, the same step on the
+    CPU)."""
+
+    def __init__(self, plan: Optional[RoutingPlan], n_hosts: int, table_slots_min: int, note_cap: int, log_cap: int):
+        self.plan = plan
+        self.n_hosts = int(n_hosts)
+        self._h = C.c_void_p()
+        if plan is not None:
+            _bind_to_plan(self, plan)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_deliver_create(plan.handle if plan is not None else None, self.n_hosts,
+                                                 int(table_slots_min), int(note_cap), int(log_cap),
+                                                 C.byref(self._h), C.byref(err)), err)
+
+    _ptr = staticmethod(InboundRouter._ptr)
+    _nbytes = staticmethod(SendBatch._nbytes)
+    _streams = FlightStore._streams
+
+    def associate(self, assoc):
+        """srt_deliver_associate: ASSOC_DTYPE records (a host numpy array).
+        Raises SrtError, and adds nothing, when a key exists already."""
+        a = np.ascontiguousarray(assoc, ASSOC_DTYPE)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_deliver_associate(self._h, a.ctypes.data, len(a), C.byref(err)), err)
+
+    def disassociate(self, assoc):
+        """srt_deliver_disassociate: ASSOC_DTYPE records; `socket` is ignored, a missing key is a no-op."""
+        a = np.ascontiguousarray(assoc, ASSOC_DTYPE)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_deliver_disassociate(self._h, a.ctypes.data, len(a), C.byref(err)), err)
+
+    def lookup(self, hosts, meta) -> np.ndarray:
+        """srt_deliver_lookup on the host: the socket of every (host, RX_META_DTYPE record), 0xffffffff: none."""
+        h = np.ascontiguousarray(hosts, np.uint32)
+        m = np.ascontiguousarray(meta, RX_META_DTYPE)
+        if len(h) != len(m):
+            raise ValueError("DeliverStage.lookup: hosts and meta differ in length")
+        out = np.zeros(len(h), np.uint32)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_deliver_lookup(self._h, h.ctypes.data, m.ctypes.data, len(h), out.ctypes.data,
+                                                 C.byref(err)), err)
+        return out
+
+    def table_stats(self):
+        """srt_deliver_table_stats -> (associations, slots, longest probe sequence, a chain wraps the end)"""
+        n, s, p, w, err = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint32(), _lib.SrtErr()
+        _lib.check(_lib.lib().srt_deliver_table_stats(self._h, C.byref(n), C.byref(s), C.byref(p), C.byref(w),
+                                                      C.byref(err)), err)
+        return n.value, s.value, p.value, bool(w.value)
+
+    def note(self, meta, tag_base: int):
+        """srt_deliver_note after FlightStore.push (tag=None) of a round: meta, a
+        uint8 view of the round's 16-byte srt_rx_meta records, one a batch
+        packet; tag_base as the push returned it."""
+        n_pkts = self._nbytes(meta) // 16
+        cur, ps = self._streams(meta) if n_pkts else (None, None)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_deliver_note(self._h, self._ptr(meta), n_pkts, int(tag_base), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)
+
+    def run(self, dst_ptr, tag, status, forward_ns, seq_base: int, late, late_count, out_host_ptr, out_socket,
+            out_forward_ns, out_tag, out_user, out_status):
+        """srt_deliver_run on the arrays of the InboundRouter.run call just made:
+        dst_ptr int32/uint32 [n_hosts+1] and tag int64/uint64 (FlightStore.pop's
+        w_dst_ptr and w_tag), status int32/uint32 (its size is n_pkts) and
+        forward_ns int64/uint64, its return value as seq_base, late (a uint8
+        buffer of 24-byte records) and late_count.  Outputs: out_host_ptr
+        int32/uint32 [n_hosts+1]; out_socket int32/uint32 (its size is out_cap),
+        out_forward_ns and out_tag int64/uint64, out_user and out_status
+        int32/uint32, [out_cap] each.  Device form: enqueue only (status()
+        synchronises)."""
+        n_pkts = self._nbytes(status) // 4
+        late_cap = self._nbytes(late) // 24
+        out_cap = self._nbytes(out_socket) // 4
+        if self._nbytes(dst_ptr) < 4 * (self.n_hosts + 1) or self._nbytes(out_host_ptr) < 4 * (self.n_hosts + 1) or \
+                self._nbytes(tag) < 8 * n_pkts or self._nbytes(forward_ns) < 8 * n_pkts or \
+                self._nbytes(out_forward_ns) < 8 * out_cap or self._nbytes(out_tag) < 8 * out_cap or \
+                self._nbytes(out_user) < 4 * out_cap or self._nbytes(out_status) < 4 * out_cap:
+            raise ValueError("DeliverStage.run: an array is smaller than its record count")
+        cur, ps = self._streams(out_host_ptr)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_deliver_run(
+            self._h, self._ptr(dst_ptr), n_pkts, self._ptr(tag), self._ptr(status), self._ptr(forward_ns),
+            int(seq_base), self._ptr(late), late_cap, self._ptr(late_count), self._ptr(out_host_ptr),
+            self._ptr(out_socket), self._ptr(out_forward_ns), self._ptr(out_tag), self._ptr(out_user),
+            self._ptr(out_status), out_cap, C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)  # torch-side consumers see the outputs (device-side ordering)
+
+    def status(self, check: bool = True):
+        """srt_deliver_status: synchronises; (flags, delivered packets of the
+        last run, those no socket took).  check=True raises SrtError when a
+        flag is set."""
+        flags, n, miss = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        err = _lib.SrtErr()
+        rc = _lib.lib().srt_deliver_status(self._h, C.byref(flags), C.byref(n), C.byref(miss), C.byref(err))
+        if check or (rc != _lib.SRT_OK and not flags.value):
+            _lib.check(rc, err)
+        return flags.value, n.value, miss.value
+
+    def close(self):
+        if self._h:
+            _lib.lib().srt_deliver_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def outbound_send_order(host_ptr, send_rank, late_src_host=None, late_send_rank=None):
     """The grouped send order srt_packet_batch needs, from a round's
     OutboundRelay.run outputs, with torch ops on the tensors' device.
