@@ -409,6 +409,12 @@ __device__ unsigned long long lvl_cnt[8][5];  // level solve, per level (<= 7): 
 __constant__ uint32_t lvl_diag;                // level solve ablations (SRT_LVL_DIAG)
 #endif
 #define LOSS_TICK(slot) LOSS_TICK_TO(solve_cnt, slot)
+// the packed push: 1 keeps the state probe of the head's key as the select's
+// predicate (a read before every min; C3 4.29 ms a step), 0 mins
+// unconditionally (4.32; A/B builds)
+#ifndef SRT_PK_PROBE
+#define SRT_PK_PROBE 1
+#endif
 // probe != nullptr: no table; probe[2 + k] = the largest level over the
 // in-use columns of row k (0xffff if one is unreached by level lcap), the u64
 // at probe[0] += the edges walked.
@@ -465,13 +471,19 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
     const int lane = tid & 63, wv = tid >> 6, nw = nt >> 6;
     const uint32_t grp = tid / LPT, sub = tid % LPT, ngrp = nt / LPT;
     const uint64_t below = (1ull << lane) - 1ull;
-    uint64_t mn = ~0ull;
-    unsigned long long unreach = 0, visits = 0;
+    // The launch's minimum, unreached and visit counts live in the static LDS
+    // reductions (a wave's slot, its lane 0 the only writer), folded in at each
+    // row's end: none of them holds registers across the walk.
+    if (tid < 16) {
+        red_min[tid] = ~0ull;
+        red_cnt[tid] = red_vis[tid] = 0;
+    }
     const uint32_t nrows = row_list ? row1 : row1 - row0;
     // rows dealt by a counter (row_ctr != nullptr; else statically, row k to
-    // workgroup k mod grid): a workgroup takes its next row one row ahead (the
-    // atomic's latency behind the row's work), so a CU whose rows ran long
-    // takes fewer; every workgroup makes exactly one fetch past the last row
+    // workgroup k mod grid): a workgroup takes its next row while it writes
+    // the row before (the atomic's latency behind the output phase), so a CU
+    // whose rows ran long takes fewer; every workgroup makes exactly one fetch
+    // past the last row
     unsigned long long kn = 0;
     auto fetch = [&]() -> uint32_t {
         if (tid == 0) dyn_k = (uint32_t)(kn < nrows ? kn : nrows);
@@ -482,7 +494,8 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
     uint32_t k0 = blockIdx.x;
     if (row_ctr) k0 = fetch();
     for (uint32_t k = k0; k < nrows; k = row_ctr ? fetch() : k + gridDim.x) {
-        if (row_ctr && tid == 0) kn = atomicAdd(&row_ctr[0], 1ull);  // the next row
+        uint64_t mn = ~0ull;
+        uint32_t unreach = 0, vis32 = 0;  // this row's, a lane (a row's entries and columns are < 2^32)
         const uint32_t i = row_list ? row_list[k] : row0 + k;
         const uint32_t s = nodes[i];
 #if LOSS_COUNT
@@ -715,54 +728,82 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                         uint64_t wd[NE];
                         uint32_t o[NE];
                         bool ok[NE];
+                        // the lane's slots: slot s (pair q = s / 2 at 2 LPT q) holds
+                        // entry a0 + s, inside the list from s_lo on and below s_hi
+                        // (s_lo <= 1: the chunk starts at the even entry at or
+                        // below e0) -- one compare a slot but the first
+                        const uint32_t a0 = cb + 2 * sub;
+                        const int32_t s_lo = (int32_t)(ce0 - a0), s_hi = (int32_t)(ce1 - a0);
 #pragma unroll
                         for (int q = 0; q < UNR; ++q) {
                             wd[2 * q] = ((uint64_t)cur[q].y << 32) | cur[q].x;
                             wd[2 * q + 1] = ((uint64_t)cur[q].w << 32) | cur[q].z;
-                            const uint32_t at = cb + (sub + q * LPT) * 2;
-                            ok[2 * q] = at < ce1 && at >= ce0;
-                            ok[2 * q + 1] = at + 1 < ce1;  // at + 1 >= ce0: at >= ce0 & ~1
+                            ok[2 * q] = 2 * LPT * q < s_hi && (q > 0 || s_lo <= 0);
+                            ok[2 * q + 1] = 2 * LPT * q + 1 < s_hi;
                         }
-#pragma unroll
-                        for (int q = 0; q < NE; ++q) o[q] = ok[q] ? (uint32_t)wd[q] : 0u;
+                        // every entry of [e0, e1) is walked once, also under the K
+                        // spread: the lane group that takes an item's first chunk
+                        // counts the whole list
+                        vis32 += sub == 0 && cb == (ce0 & ~1u) ? ce1 - ce0 : 0u;
                         if constexpr (PK) {
+                            // A slot outside the list aims at the item's own
+                            // vertex: settled on push, unsettled on pull, so it is
+                            // no hit and its min is a no-op.
 #pragma unroll
-                            for (int q = 0; q < NE; ++q) visits += ok[q];
+                            for (int q = 0; q < NE; ++q) o[q] = ok[q] ? (uint32_t)wd[q] : cx;
                             if ((pm >> cw) & 1ull) {
-                                // push: the head's key, unless settled (state 0),
-                                // takes state 1 and the min of the candidates
+                                // push: the head's key takes state 1 and the min of
+                                // the candidates.  Branch-free: a candidate is
+                                // above every settled key (state 0 < 1 << 30) and
+                                // all ones lowers no key, so the NE mins go out
+                                // back to back without an exec-mask region each.
+                                const float onem = 1.0f - __uint_as_float(key[cx] & PACK_LOSS);
+                                uint32_t c[NE];
+#if SRT_PK_PROBE
                                 uint32_t ko[NE];
 #pragma unroll
                                 for (int q = 0; q < NE; ++q) ko[q] = key[o[q]];
-                                const float onem = 1.0f - __uint_as_float(key[cx] & PACK_LOSS);
+#endif
 #pragma unroll
-                                for (int q = 0; q < NE; ++q)
-                                    if (ok[q] && (ko[q] >> 30)) {
-                                        const float r = __uint_as_float((uint32_t)(wd[q] >> 32));
-                                        const uint32_t c = __float_as_uint(1.0f - __fmul_rn(onem, r));
-                                        atomicMin(&key[o[q]], 1u << 30 | (c & PACK_LOSS));
-                                    }
+                                for (int q = 0; q < NE; ++q) {
+                                    const float r = __uint_as_float((uint32_t)(wd[q] >> 32));
+                                    const uint32_t b = __float_as_uint(1.0f - __fmul_rn(onem, r));
+#if SRT_PK_PROBE
+                                    c[q] = ko[q] > PACK_LOSS ? 1u << 30 | (b & PACK_LOSS) : ~0u;
+#else
+                                    c[q] = ok[q] ? 1u << 30 | (b & PACK_LOSS) : ~0u;
+#endif
+                                }
+#pragma unroll
+                                for (int q = 0; q < NE; ++q) atomicMin(&key[o[q]], c[q]);
                             } else {
-                                // pull: the tail's 4-bit level against j; a tail at j is settled
+                                // pull: the tail's 4-bit level against j (<= 13, never
+                                // the unsettled 0xF); a tail at j is settled.  The
+                                // tails' losses are read for every slot (any o is a
+                                // vertex), the lane's candidates folded in registers.
                                 const uint32_t j = l - cw;
-                                uint32_t lo4[NE];
+                                uint32_t lo4[NE], ku[NE];
 #pragma unroll
                                 for (int q = 0; q < NE; ++q) lo4[q] = lev_of(o[q]);
 #pragma unroll
-                                for (int q = 0; q < NE; ++q)
-                                    if (ok[q] && lo4[q] == j) {
-                                        const float r = __uint_as_float((uint32_t)(wd[q] >> 32));
-                                        const float lu = __uint_as_float(key[o[q]] & PACK_LOSS);
-                                        const uint32_t c = __float_as_uint(1.0f - __fmul_rn(1.0f - lu, r));
-                                        atomicMin(&key[cx], 1u << 30 | (c & PACK_LOSS));
-                                    }
+                                for (int q = 0; q < NE; ++q) ku[q] = key[o[q]];
+                                uint32_t best = ~0u;
+#pragma unroll
+                                for (int q = 0; q < NE; ++q) {
+                                    const float r = __uint_as_float((uint32_t)(wd[q] >> 32));
+                                    const float lu = __uint_as_float(ku[q] & PACK_LOSS);
+                                    const uint32_t b = __float_as_uint(1.0f - __fmul_rn(1.0f - lu, r));
+                                    const uint32_t c = lo4[q] == j ? 1u << 30 | (b & PACK_LOSS) : ~0u;
+                                    best = c < best ? c : best;
+                                }
+                                if (best != ~0u) atomicMin(&key[cx], best);
                             }
                         } else {
+#pragma unroll
+                            for (int q = 0; q < NE; ++q) o[q] = ok[q] ? (uint32_t)wd[q] : 0u;
                             uint16_t lo_[NE];
 #pragma unroll
                             for (int q = 0; q < NE; ++q) lo_[q] = lrow[o[q]];
-#pragma unroll
-                            for (int q = 0; q < NE; ++q) visits += ok[q];
                             if ((pm >> cw) & 1ull) {
                                 // push: x in N_j, its class-w out-edges x -> v, v
                                 // unsettled or at l: v enters level l (stored once),
@@ -828,7 +869,7 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                         for (int q = 0; q < NE; ++q) lo_[q] = lrow[o[q]];
 #pragma unroll
                         for (int q = 0; q < NE; ++q) {
-                            visits += ok[q];
+                            vis32 += ok[q];
                             const bool hit = ok[q] && (push ? lo_[q] >= (uint16_t)l : lo_[q] == (uint16_t)j);
                             if (hit) {
                                 // the head enters level l (every writer stores l; a
@@ -869,6 +910,21 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
         }
         __syncthreads();  // hist / lrow final for the output
         LOSS_TICK(6)
+        if (row_ctr && tid == 0) kn = atomicAdd(&row_ctr[0], 1ull);  // the next row
+        // this row's counts into the wave's slots of the static reductions
+        auto row_fold = [&]() {
+            for (int off = 32; off > 0; off >>= 1) {
+                const uint64_t o = __shfl_xor(mn, off);
+                mn = o < mn ? o : mn;
+                unreach += __shfl_xor(unreach, off);
+                vis32 += __shfl_xor(vis32, off);  // (a row's visits: < 2^32 entries)
+            }
+            if (lane == 0) {
+                red_min[wv] = mn < red_min[wv] ? mn : red_min[wv];
+                red_cnt[wv] += unreach;
+                red_vis[wv] += vis32;
+            }
+        };
         // 3. table row i (or staging slot k), or the probe's row maximum
         if (probe) {  // (probe rows run the unpacked row: their caps are 15, 31, 63)
             uint32_t rmax = 0;
@@ -887,6 +943,7 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                 for (int q = 0; q < nw; ++q) m = red_max[q] > m ? red_max[q] : m;
                 probe[2 + k] = m;
             }
+            row_fold();
             __syncthreads();
             continue;
         }
@@ -1004,24 +1061,11 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                 mn = latv < mn ? latv : mn;
             }
         }
+        row_fold();
         __syncthreads();  // the next row rewrites the LDS rows
         LOSS_TICK(7)
     }
-#if LOSS_COUNT
-    if (!probe) atomicAdd(&solve_cnt[1], visits);
-#endif
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t o = __shfl_xor(mn, off);
-        mn = o < mn ? o : mn;
-        unreach += __shfl_xor(unreach, off);
-        visits += __shfl_xor(visits, off);
-    }
-    if (lane == 0) {
-        red_min[wv] = mn;
-        red_cnt[wv] = unreach;
-        red_vis[wv] = visits;
-    }
-    __syncthreads();
+    __syncthreads();  // (a workgroup without a row: the slots' initial values)
     if (tid == 0) {
         unsigned long long m = red_min[0], c = red_cnt[0], vz = red_vis[0];
         for (int q = 1; q < nw; ++q) {
@@ -1029,6 +1073,9 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
             c += red_cnt[q];
             vz += red_vis[q];
         }
+#if LOSS_COUNT
+        if (!probe) atomicAdd(&solve_cnt[1], vz);
+#endif
         if (probe) {
             if (vz) atomicAdd(reinterpret_cast<unsigned long long *>(probe), vz);
         } else {
