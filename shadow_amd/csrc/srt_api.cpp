@@ -612,6 +612,7 @@ void read_create_knobs(CreateKnobs &k) {
     read("SRT_LVL_DYN", k.lvl_dyn, as_int);
     read("SRT_LVL_PACK", k.lvl_pack, as_int);
     read("SRT_LVL_SPREAD", k.lvl_spread, as_int);
+    read("SRT_LVL_LEAN", k.lvl_lean, as_int);
     read("SRT_FW_P1", k.fw_p1, as_int);
     read("SRT_FW_EMULATE_RANKS", k.fw_emulate_ranks, as_int);
     read("SRT_FW_BAND", k.fw_band, [](const char *e) { return e[0] == '1'; });
@@ -973,6 +974,8 @@ srt_status choose_family(Create &c) {
                           ? 2u
                           : 0u;
         p->lvl_spread = !(c.knobs.lvl_spread.set && c.knobs.lvl_spread.v == 0);
+        p->lvl_lean = !c.knobs.lvl_lean.set || c.knobs.lvl_lean.v == 1 ? srt::LVL_LEAN_KEPT
+                                                                        : (uint32_t)c.knobs.lvl_lean.v & srt::LVL_LEAN_ALL;
         p->desc = srt::describe_level(p->kp.g, p->lvl_q, p->kp.lmax, p->V, n, c.lvl_visits, p->lvl_sym,
                                       p->d_lat16 != nullptr, p->lvl_pack != 0);
     } else {

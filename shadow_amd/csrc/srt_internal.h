@@ -47,6 +47,13 @@ constexpr int FW_B = 128;
 // level solve (SRT_ALGO_LEVEL): the row (u16 level, f32 loss, u16 member per
 // vertex) in the 160 KB LDS beside the 8 KB level table
 constexpr uint32_t LEVEL_V_MAX = 18400;
+// ... its stages that spare full-row passes around a level's walk (knob
+// SRT_LVL_LEAN; level_solve_kernel's `lean`): small push levels of the packed
+// row list their members instead of a scan of the row, and its `idn` output
+// pass leaves the row initialised for the workgroup's next one
+constexpr uint32_t LVL_LEAN_LIST = 2, LVL_LEAN_INIT = 4;
+constexpr uint32_t LVL_LEAN_ALL = LVL_LEAN_LIST | LVL_LEAN_INIT;
+constexpr uint32_t LVL_LEAN_KEPT = LVL_LEAN_ALL;
 
 // In-edge of the sparse SSSP (srt_sssp.hip): the source vertex u of an
 // adjacency entry u -> v, its latency in units of g and 1 - loss rounded to f32
@@ -358,6 +365,7 @@ struct srt_plan {
     unsigned long long *d_rowctr = nullptr;  // level solve: the rows dealt by a counter (LevelCtx::row_ctr)
     uint32_t lvl_pack = 0;                   // the packed LDS row: its workgroups a CU (0: the unpacked row), chosen at create (choose_row_packed)
     bool lvl_spread = true;                  // ... with K lane groups an item in small levels (knob SRT_LVL_SPREAD=0: one)
+    uint32_t lvl_lean = srt::LVL_LEAN_KEPT;  // ... and these LVL_LEAN_* stages around the walk (knob SRT_LVL_LEAN=0: none)
     bool lvl_nt = true, lvl_sp = true, lvl_dyn = true;  // its launch knobs, read at create (CreateKnobs): LevelCtx::nt_store, sp, row_ctr
     unsigned long long *d_lvisit = nullptr;  // level solve: class entries the last run walked
     uint32_t lvl_q = 0, lvl_rb = 0, lvl_vb = 0;  // quantized level solve: bucket width (units), entry field bits
@@ -508,6 +516,7 @@ struct LevelCtx {
     bool sp = true;                        // the pipelined class walk (false: the per-item walk)
     uint32_t pack = 0;                     // packed-row workgroups a CU (srt_plan::lvl_pack; 0: the unpacked row); needs lmem
     bool spread = true;                    // packed row: K lane groups an item in small levels
+    uint32_t lean = LVL_LEAN_KEPT;         // the LVL_LEAN_* stages around the walk (srt_plan::lvl_lean)
 };
 LevelCtx level_ctx(srt_plan *p);
 // the class CSRs of a level plan at its bound (the run's first step)

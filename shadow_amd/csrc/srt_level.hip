@@ -415,6 +415,16 @@ __constant__ uint32_t lvl_diag;                // level solve ablations (SRT_LVL
 #ifndef SRT_PK_PROBE
 #define SRT_PK_PROBE 1
 #endif
+// The lean stages (`lean`, LVL_LEAN_* of srt_internal.h; SRT_LVL_LEAN=0: none).
+// LIST_T: a push-only level of the packed row with at most so many items is
+// walked LIST_LPI lanes an item and lists its members as they are hit, instead
+// of a scan of the row for them (`lean` carries it in its high half, 0: never).
+#ifndef SRT_LIST_T
+#define SRT_LIST_T 16
+#endif
+constexpr uint32_t LIST_T = SRT_LIST_T;
+constexpr uint32_t LIST_LPI = PACK_NT / LIST_T;  // lanes an item of a listed level
+static_assert(LIST_T >= 1 && LIST_T * LIST_LPI == PACK_NT, "a listed level's items share the workgroup evenly");
 // probe != nullptr: no table; probe[2 + k] = the largest level over the
 // in-use columns of row k (0xffff if one is unreached by level lcap), the u64
 // at probe[0] += the edges walked.
@@ -447,7 +457,7 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
     unsigned long long *stats, const uint32_t *__restrict__ row_list, void *__restrict__ out32,
     float *__restrict__ out32_loss, bool stage16, uint32_t *__restrict__ probe,
     unsigned long long *__restrict__ visit_cnt, bool idn, unsigned long long *row_ctr, uint16_t *mem_all,
-    bool spread) {
+    bool spread, uint32_t lean) {
     static_assert(!PK || (SP && CLSN == 16), "the packed row: the pipelined walk, levels <= PACK_LMAX");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ unsigned long long red_min[16], red_cnt[16], red_vis[16];
@@ -464,6 +474,8 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
     uint16_t *mem = PK ? mem_all + (uint64_t)blockIdx.x * V : reinterpret_cast<uint16_t *>(smem + lds_mem_off(SOLVE_HIST, V));
     uint32_t *key = reinterpret_cast<uint32_t *>(smem + SOLVE_HIST);  // PK: state | loss bits
     uint16_t *lev = reinterpret_cast<uint16_t *>(smem + pack_lev_off(V));  // PK: the levels of quad k in word k
+    uint32_t *lev32 = reinterpret_cast<uint32_t *>(smem + pack_lev_off(V));  // ... the words of quads 2 k, 2 k + 1
+    const uint32_t list_t = PK ? lean >> 16 : 0u;
     auto lev_of = [&](uint32_t v) -> uint32_t { return ((uint32_t)lev[v >> 2] >> (4 * (v & 3u))) & 0xfu; };
     const uint16_t LINF = 0xffffu;
     const uint32_t FINF = 0x7f800000u;  // +inf bits
@@ -478,6 +490,7 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
         red_min[tid] = ~0ull;
         red_cnt[tid] = red_vis[tid] = 0;
     }
+    bool clean = false;  // PK: the output pass before left every key and level unreached (uniform)
     const uint32_t nrows = row_list ? row1 : row1 - row0;
     // rows dealt by a counter (row_ctr != nullptr; else statically, row k to
     // workgroup k mod grid): a workgroup takes its next row while it writes
@@ -503,7 +516,13 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
 #endif
         // 1. every vertex unreached, s at level 0 (petgraph's zero score);
         // four vertices a thread a step (8-B level and 16-B loss stores)
-        if constexpr (PK) {
+        if (PK && clean) {
+            // the row before's output pass stored the unreached pattern behind its reads: s alone is patched
+            if (tid == 0) {
+                key[s] = 0u;
+                lev[s >> 2] = (uint16_t)(0xffffu & ~(0xfu << (4 * (s & 3u))));
+            }
+        } else if constexpr (PK) {
             // (the last quad's vertices past V stay unreached / 0xF: never read)
             for (uint32_t v4 = 4 * tid; v4 < V; v4 += 4 * nt) {
                 const uint32_t q = s - v4;  // s among them: state 0, loss 0, level 0
@@ -675,6 +694,28 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                 e0 = cl[(uint64_t)x * CLSN + w - 1];
                 e1 = cl[(uint64_t)x * CLSN + w];
             };
+            // PK: a push-only level of few items (uniform) does not scan the row for its
+            // members: LIST_LPI lanes an item walk its list entry by entry, the hit's min
+            // is the returning form, and the one lane that finds the head unreached
+            // (state 3; every later hit finds state 1) appends it to the members
+            bool listed = false;
+            if constexpr (PK) listed = T <= list_t && !plan_pull;
+            if (PK && listed) {
+                const uint32_t t = tid / LIST_LPI, ls = tid % LIST_LPI;
+                if (t < T) {
+                    uint32_t w = 1, x, e0, e1;
+                    item(t, w, x, e0, e1);
+                    vis32 += ls == 0 ? e1 - e0 : 0u;
+                    const float onem = 1.0f - __uint_as_float(key[x] & PACK_LOSS);
+                    for (uint32_t e = e0 + ls; e < e1; e += LIST_LPI) {
+                        const uint64_t wd = ce_out[e];
+                        const uint32_t o = (uint32_t)wd;
+                        const uint32_t b = __float_as_uint(1.0f - __fmul_rn(onem, __uint_as_float((uint32_t)(wd >> 32))));
+                        if (key[o] > PACK_LOSS && atomicMin(&key[o], 1u << 30 | (b & PACK_LOSS)) >= 3u << 30)
+                            mem[settled + atomicAdd(&cur[par][1], 1u)] = (uint16_t)o;
+                    }
+                }
+            } else
             if constexpr (SP) {
                 // The level's items as one stream of chunks a lane group (CH
                 // entries of one item's class list, UNR pairs a lane): the next
@@ -902,7 +943,18 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
             __syncthreads();  // every head of level l found
             LVL_TICK(1)
             // N_l (the vertices now at level l) -> mem[settled, ...)
-            compact((uint16_t)l, settled, par, 1);
+            if (PK && listed) {
+                // the listed members alone: the state cleared, the 4-bit level by an atomic on
+                // the 32-bit word of the vertex's quad pair (up to 8 members share it)
+                const uint32_t got = cur[par][1];
+                for (uint32_t m = tid; m < got; m += nt) {
+                    const uint32_t v = mem[settled + m];
+                    key[v] &= PACK_LOSS;
+                    atomicAnd(&lev32[v >> 3], ~((0xfu ^ l) << (4 * (v & 7u))));
+                }
+            } else {
+                compact((uint16_t)l, settled, par, 1);
+            }
             __syncthreads();
             LVL_TICK(2)
             settled += cur[par][1];
@@ -960,11 +1012,19 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
             typedef float f32x4 __attribute__((ext_vector_type(4)));
             typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
             typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+            // PK: the unreached pattern stored back behind a quad's reads (this loop covers the
+            // row: n = V), so that the workgroup's next row patches its source alone
+            const bool reinit = PK && (lean & LVL_LEAN_INIT);
+            clean = reinit;
             for (uint32_t j4 = 4 * tid; j4 < n; j4 += 4 * nt) {
                 // (PK: one 2-B word of levels, 0xF = unreached, and the 16 B of keys)
                 const uint32_t l4 = PK ? lev[j4 >> 2] : 0u;
                 const uint2 lw = PK ? make_uint2(0u, 0u) : *reinterpret_cast<const uint2 *>(lrow + j4);
                 const uint4 pw = *reinterpret_cast<const uint4 *>((PK ? key : prow) + j4);
+                if (reinit) {
+                    lev[j4 >> 2] = (uint16_t)0xffffu;
+                    *reinterpret_cast<uint4 *>(key + j4) = make_uint4(~0u, ~0u, ~0u, ~0u);
+                }
                 auto lv4 = [&](int q) -> uint32_t {
                     const uint32_t x = (l4 >> (4 * q)) & 0xfu;
                     return x == 0xfu ? (uint32_t)LINF : x;
@@ -1445,6 +1505,10 @@ LevelCtx level_ctx(srt_plan *p) {
     c.sp = p->lvl_sp;
     c.pack = p->lvl_pack;
     c.spread = p->lvl_spread;
+    // (the packed row's listed levels: LIST_T items at most; SRT_LVL_LIST_T: fewer, A/B)
+    const char *lt = std::getenv("SRT_LVL_LIST_T");
+    const uint32_t list_t = std::min<uint32_t>(lt ? (uint32_t)std::atoi(lt) : LIST_T, LIST_T);
+    c.lean = p->lvl_lean | (p->lvl_lean & LVL_LEAN_LIST ? list_t << 16 : 0u);
     // rows dealt by a counter (knob SRT_LVL_DYN=0: statically, A/B)
     const bool dyn = p->lvl_dyn;
     if (dyn && !p->d_rowctr) {
@@ -1781,7 +1845,7 @@ void launch_solve_ctx(const LevelCtx &c, unsigned long long *d_stats, const uint
     hipLaunchKernelGGL(kern, dim3(grid), dim3(nt), lds, c.stream, V, c.nodes, c.n, list ? 0u : r0, r1, co, ci, eo, ei,
                        lcap, c.g, c.sl_lat, c.sl_loss, c.out_lat, c.out_loss, d_stats, list,
                        stage_mode ? stage : nullptr, stage_mode ? stage_loss : nullptr, stage_mode == 1, probe,
-                       c.visits, c.idn, c.row_ctr, pack ? c.lmem : (uint16_t *)nullptr, c.spread);
+                       c.visits, c.idn, c.row_ctr, pack ? c.lmem : (uint16_t *)nullptr, c.spread, c.lean);
 }
 
 // the per-workgroup scratch of the quantized solve and of the packed row
