@@ -544,8 +544,9 @@ void srt_inbound_destroy(srt_inbound *ib);
  * close, say); a caller that disassociates a socket mid-window must treat the
  * window's later deliveries to that socket as the lookup would, or split the
  * window there.
- * OUT OF SCOPE: pcap capture, the tracker's byte counts, what the socket does
- * with the packet, the loopback relay, the CPU-delay model.
+ * OUT OF SCOPE: pcap capture, what the socket does with the packet, the
+ * loopback relay, the CPU-delay model.  (The tracker's byte counts of the
+ * internet interface are the srt_tracker stage below.)
  * ABI: additive to version 4; detect the stage by its symbols. */
 typedef struct srt_deliver srt_deliver;
 
@@ -827,6 +828,11 @@ srt_status srt_outbound_run(srt_outbound *ob, const srt_out_pkt *d_pkts, const u
 srt_status srt_outbound_status(srt_outbound *ob, uint32_t *flags, uint64_t *n_pending, srt_err *err);
 /* Synchronises and copies every host's state to out[n_hosts] (HOST pointer). */
 srt_status srt_outbound_state(srt_outbound *ob, srt_outbound_host_state *out, srt_err *err);
+/* d_seq[h] (n_hosts entries) = the sequence number of the packet host h's relay
+ * holds cached at the end of the last srt_outbound_run, or UINT64_MAX when it
+ * holds none.  Asynchronous on the plan's stream (host-only: a plain loop).
+ * For srt_tracker_tx below. */
+srt_status srt_outbound_cached_seq(srt_outbound *ob, uint64_t *d_seq, srt_err *err);
 void srt_outbound_destroy(srt_outbound *ob);
 
 /* ------------------------------------------------------ send-batch gather */
@@ -906,6 +912,173 @@ srt_status srt_sendbatch_run(srt_sendbatch *sb, const uint32_t *d_host_ptr, uint
  * names every flag set, when any was; else SRT_OK. */
 srt_status srt_sendbatch_status(srt_sendbatch *sb, uint32_t *flags, uint64_t *n_sent, srt_err *err);
 void srt_sendbatch_destroy(srt_sendbatch *sb);
+
+/* --------------------------------------------------- tracker byte counters */
+/* The tracker's heartbeat counters for the internet interface, on the device:
+ * what tracker_addOutputBytes (called in networkinterface_pop,
+ * host/network/network_interface.c:310-340) and tracker_addInputBytes (called
+ * in networkinterface_push, :140-202) add up between two heartbeats
+ * (host/tracker.c:24-48, 188-284), and what tracker_heartbeat logs as
+ * "[shadow-heartbeat] [node]" and "[socket]" and then clears (:400-433,
+ * 582-627).  A packet with payload > 0 is data, else control;
+ * PDS_SND_TCP_RETRANSMITTED (SRT_TRK_RETRANS) selects the retransmit class.
+ * Counts are kept per host and, separately, per socket slot, each in and out.
+ * Only the REMOTE counters are kept: local means the loopback address, and on
+ * the internet interface every packet is remote, one addressed to the
+ * interface's own address (SRT_OUT_LOCAL) included, since its source is not
+ * 127.0.0.1.
+ * Output side: a packet is counted when the interface pops it, the moment it
+ * gets SND_INTERFACE_SENT, before the relay may cache it and whether or not it
+ * is forwarded later.  Input side: a packet is counted at networkinterface_push
+ * and only if a socket took it (RCV_INTERFACE_DROPPED is not counted).
+ * LIMITS: a call's packets all count in the current interval: the caller ends a
+ * window at a heartbeat time and calls srt_tracker_heartbeat between windows.
+ * The reference orders a heartbeat task and a packet event of the same instant
+ * by event id, which the library does not own.
+ * OUT OF SCOPE: the loopback interface (the tracker's local counters), the
+ * tracker's CPU, memory and socket-buffer lines, pcap capture.
+ * ABI: additive to version 4; detect the stage by its symbols. */
+typedef struct srt_tracker srt_tracker;
+
+/* Counters (tracker.c:24-48) in the order of the heartbeat line, 80 bytes */
+typedef struct {
+    uint64_t packets_control;
+    uint64_t bytes_control_header;
+    uint64_t packets_control_retrans;
+    uint64_t bytes_control_header_retrans;
+    uint64_t packets_data;
+    uint64_t bytes_data_header;
+    uint64_t bytes_data_payload;
+    uint64_t packets_data_retrans;
+    uint64_t bytes_data_header_retrans;
+    uint64_t bytes_data_payload_retrans;
+} srt_trk_counters;
+
+#define SRT_TRK_RETRANS 1u /* srt_trk_meta.flags: the packet's status has PDS_SND_TCP_RETRANSMITTED */
+
+/* what the tracker needs from a packet beyond what the other stages return, 16 bytes */
+typedef struct {
+    uint32_t header_size;  /* packet_getHeaderSize */
+    uint32_t payload_size; /* packet_getPayloadSize */
+    uint32_t flags;        /* SRT_TRK_RETRANS */
+    uint32_t socket_slot;  /* output side: the sending socket's slot (the input side takes srt_deliver's socket) */
+} srt_trk_meta;
+
+#define SRT_TRACKER_LOG_OVERRUN  1u /* a late or cached packet's seq is older than the log holds: not counted */
+#define SRT_TRACKER_NOTE_OVERRUN 2u /* a placeholder delivery record, or a tag the note ring does not hold: skipped */
+#define SRT_TRACKER_BAD_SOCKET   4u /* a socket slot >= n_sockets: counted at its host only */
+#define SRT_TRACKER_BAD_HOST     8u /* a late or flat record's host >= n_hosts: skipped */
+
+/* An instance for n_hosts hosts and n_sockets socket slots on the plan's device
+ * and stream, or, with plan == NULL, host-only: every array argument named d_
+ * is then a HOST pointer and the calls complete before they return.  Both forms
+ * run the same step and agree bit for bit (all sums are integers).  The slots
+ * are global and chosen by the caller: on the send side a packet's slot is
+ * srt_trk_meta.socket_slot, on the receive side it is the socket
+ * srt_deliver_run returns, so a caller who wants socket counters names its
+ * associations by slot.  n_sockets == 0 switches the socket counters off.
+ * Memory of the instance, in bytes:
+ *   32 + n_hosts * 184 + n_sockets * 160 + (note_cap + log_cap) * 16
+ * (the state words; per host the in and out records, two packet counts and
+ * the remembered cached seq; per slot the in and out records; the note ring
+ * and the seq log of srt_trk_meta), on the device, plus the records once more
+ * on the host for the heartbeat.  Nothing is allocated per call.  n_hosts and
+ * n_sockets are below 2^31, note_cap and log_cap at most 2^31.  Destroy the
+ * instance before its plan. */
+srt_status srt_tracker_create(srt_plan *plan, uint32_t n_hosts, uint32_t n_sockets, uint64_t note_cap,
+                              uint64_t log_cap, srt_tracker **out, srt_err *err);
+
+/* The output side, for the srt_outbound_run call just made: d_cached_seq is
+ * what srt_outbound_cached_seq wrote after that call, d_host_ptr, n_pkts
+ * (< 2^31) and d_status the call's arguments and output, seq_base the value it
+ * returned, d_late / late_cap (< 2^31) / d_late_count its late list, of which
+ * min(*d_late_count, late_cap) records are used.  d_meta[i] belongs to batch
+ * packet i.  A packet is counted in the call in which the interface popped it:
+ *   1. a batch packet whose d_status has SND_INTERFACE_SENT (forwarded, cached
+ *      and SRT_OUT_LOCAL packets alike);
+ *   2. a late record, unless its seq equals the seq this instance remembered
+ *      as its host's cached packet at the end of the previous call: that
+ *      packet was counted when it was popped;
+ *   3. the packet the relay holds cached at the end of this call, if its seq is
+ *      below seq_base and differs from the remembered one: queued in an earlier
+ *      call, popped and held in this one, it is neither in the batch nor in
+ *      the late list;
+ *   4. then the remembered seq becomes the cached seq, or none.
+ * So a packet cached over any number of calls is counted once, in the call
+ * that popped it.  Call it once for every srt_outbound_run call, in order.
+ * The seq log: a batch packet not popped in this call has its meta written at
+ * (seq_base + i) % log_cap iff n_pkts - i <= log_cap; the meta of a late or
+ * cached packet is read back iff its seq < seq_base and seq_base + n_pkts - seq
+ * <= log_cap, else the call is flagged LOG_OVERRUN and that packet is not
+ * counted.  Both are distances from the end of the call's range, the rule of
+ * srt_sendbatch_run, so a slot read is never one this call writes.
+ * A late record with src_host >= n_hosts is flagged BAD_HOST and skipped; a
+ * socket_slot >= n_sockets (n_sockets > 0) is flagged BAD_SOCKET and the packet
+ * counted at its host only.  Every write is range-checked first: a flagged call
+ * never writes out of bounds.
+ * Asynchronous on the plan's stream: it never waits for the device. */
+srt_status srt_tracker_tx(srt_tracker *trk, const uint64_t *d_cached_seq, const uint32_t *d_host_ptr, uint64_t n_pkts,
+                          const srt_trk_meta *d_meta, const uint32_t *d_status, uint64_t seq_base,
+                          const srt_outbound_late *d_late, uint32_t late_cap, const uint32_t *d_late_count,
+                          srt_err *err);
+
+/* The round's metas under the flight tags of its push, for the input side:
+ * the contract of srt_deliver_note (d_meta[i] has tag tag_base + i; tag_base
+ * not below the previous note's end; a tag is readable iff tag < note_end &&
+ * note_end - tag <= note_cap; n_pkts < 2^31; asynchronous). */
+srt_status srt_tracker_note(srt_tracker *trk, const srt_trk_meta *d_meta, uint64_t n_pkts, uint64_t tag_base,
+                            srt_err *err);
+
+/* The input side: srt_deliver_run's outputs as they are (d_out_host_ptr of
+ * n_hosts + 1 entries; d_out_socket, d_out_tag and d_out_status of out_cap
+ * entries).  A record is counted iff its socket is not UINT32_MAX, at its host
+ * and at the slot its socket names, with the meta noted under its tag.  A
+ * placeholder record (no RCV_INTERFACE_RECEIVED in its status), or a tag the
+ * note ring no longer holds, is skipped and flagged NOTE_OVERRUN.  The walk is
+ * bounded by min(d_out_host_ptr[n_hosts], out_cap) on the device, so out_cap
+ * may be the arrays' capacity: nothing is read back between deliver and
+ * tracker.  Asynchronous on the plan's stream. */
+srt_status srt_tracker_rx(srt_tracker *trk, const uint32_t *d_out_host_ptr, const uint32_t *d_out_socket,
+                          const uint64_t *d_out_tag, const uint32_t *d_out_status, uint64_t out_cap, srt_err *err);
+
+/* The input side for n (< 2^31) ungrouped records (host, socket, meta): the
+ * SRT_OUT_LOCAL packets, which never reach the inbound stage, with the sockets
+ * srt_deliver_lookup gave them.  A record is counted iff its socket is not
+ * UINT32_MAX; a host >= n_hosts is skipped and flagged BAD_HOST.  Duplicate
+ * (host, socket) pairs are summed.  Asynchronous on the plan's stream. */
+srt_status srt_tracker_rx_flat(srt_tracker *trk, const uint32_t *d_host, const uint32_t *d_socket,
+                               const srt_trk_meta *d_meta, uint64_t n, srt_err *err);
+
+/* tracker_heartbeat (tracker.c:582-627) for a selection of hosts and socket
+ * slots: synchronises the stream, returns the selected records and clears
+ * exactly those (the reference's memset is per host, because hosts start at
+ * different times).  hosts / sockets and the outputs are HOST pointers.  A NULL
+ * selection means all (n_hosts / n_sockets records, in index order) and its
+ * count is ignored; a selection of none is a non-NULL pointer with a count of
+ * 0.  out_node_in[k] and out_node_out[k] belong to hosts[k], out_sock_in[k] and
+ * out_sock_out[k] to sockets[k]; an output pointer may be NULL (the records are
+ * still cleared).  An index out of range returns SRT_ERR_INVALID and clears
+ * nothing; an index named twice is returned twice and cleared once. */
+srt_status srt_tracker_heartbeat(srt_tracker *trk, const uint32_t *hosts, uint32_t n_sel_hosts,
+                                 const uint32_t *sockets, uint32_t n_sel_sockets, srt_trk_counters *out_node_in,
+                                 srt_trk_counters *out_node_out, srt_trk_counters *out_sock_in,
+                                 srt_trk_counters *out_sock_out, srt_err *err);
+
+/* Synchronises the stream.  *flags (may be NULL): the SRT_TRACKER_* conditions
+ * met since the last status call (then cleared); *n_tx_counted / *n_rx_counted
+ * (may be NULL): packets counted on the output / input side since create (the
+ * device form sums the hosts' counts here, with one launch).  SRT_ERR_INVALID,
+ * with a message that names every flag set, when any was; else SRT_OK. */
+srt_status srt_tracker_status(srt_tracker *trk, uint32_t *flags, uint64_t *n_tx_counted, uint64_t *n_rx_counted,
+                              srt_err *err);
+
+/* _tracker_getCounterString (tracker.c:415-433): the twelve comma-separated
+ * numbers of a heartbeat line -- packets-total, bytes-total, then the ten
+ * fields in order -- so that a shim can emit the reference's line verbatim.
+ * Host only.  Writes at most cap bytes, NUL included; returns the length the
+ * whole string has (as snprintf does), or -1 on a NULL argument. */
+int srt_tracker_counter_string(const srt_trk_counters *c, char *buf, size_t cap);
+void srt_tracker_destroy(srt_tracker *trk);
 
 /* ---------------------------------------------------- IP assignment (a10) */
 /* IpAssignment<u32> (src/main/network/graph/mod.rs:352-420): IPv4 address ->

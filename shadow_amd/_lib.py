@@ -43,6 +43,9 @@ FLIGHT_POOL_OVERFLOW, FLIGHT_OUT_OVERFLOW, FLIGHT_BAD_HOST, FLIGHT_LATE_PUSH, FL
 # srt_assoc / srt_rx_meta protocols, srt_deliver_status flags
 PROTO_TCP, PROTO_UDP = 1, 2
 DELIVER_OUT_OVERFLOW, DELIVER_LOG_OVERRUN, DELIVER_NOTE_OVERRUN, DELIVER_BAD_HOST = 1, 2, 4, 8
+# srt_trk_meta flags, srt_tracker_status flags
+TRK_RETRANS = 1
+TRACKER_LOG_OVERRUN, TRACKER_NOTE_OVERRUN, TRACKER_BAD_SOCKET, TRACKER_BAD_HOST = 1, 2, 4, 8
 
 
 class SrtErr(C.Structure):
@@ -173,6 +176,7 @@ SIGNATURES = {
                                    C.c_uint32, _vp, _u64p, _errp]),
     "srt_outbound_status": (C.c_int, [_vp, _u32p, _u64p, _errp]),
     "srt_outbound_state": (C.c_int, [_vp, C.POINTER(SrtOutboundHostState), _errp]),
+    "srt_outbound_cached_seq": (C.c_int, [_vp, _vp, _errp]),
     "srt_outbound_destroy": (None, [_vp]),
     "srt_sendbatch_create": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.POINTER(_vp), _errp]),
     "srt_sendbatch_run": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp,
@@ -194,6 +198,15 @@ SIGNATURES = {
                                   _vp, _vp, _vp, _vp, C.c_uint64, _errp]),
     "srt_deliver_status": (C.c_int, [_vp, _u32p, _u64p, _u64p, _errp]),
     "srt_deliver_destroy": (None, [_vp]),
+    "srt_tracker_create": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(_vp), _errp]),
+    "srt_tracker_tx": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _errp]),
+    "srt_tracker_note": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _errp]),
+    "srt_tracker_rx": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _errp]),
+    "srt_tracker_rx_flat": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _errp]),
+    "srt_tracker_heartbeat": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _errp]),
+    "srt_tracker_status": (C.c_int, [_vp, _u32p, _u64p, _u64p, _errp]),
+    "srt_tracker_counter_string": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
+    "srt_tracker_destroy": (None, [_vp]),
     "srt_routing_info_build": (C.c_int, [C.POINTER(SrtCsr), _u32p, C.c_uint32, C.c_int, C.POINTER(SrtOpts),
                                          C.POINTER(_vp), _errp]),
     "srt_routing_info_from_plan": (C.c_int, [_vp, C.POINTER(_vp), _errp]),

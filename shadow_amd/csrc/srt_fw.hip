@@ -3092,6 +3092,7 @@ hipError_t preload_outbound();
 hipError_t preload_sendbatch();
 hipError_t preload_flight();
 hipError_t preload_deliver();
+hipError_t preload_tracker();
 hipError_t preload_kernels() {
     hipError_t e = preload_fw();
     if (e == hipSuccess) e = preload_loss();
@@ -3105,6 +3106,7 @@ hipError_t preload_kernels() {
     if (e == hipSuccess) e = preload_sendbatch();
     if (e == hipSuccess) e = preload_flight();
     if (e == hipSuccess) e = preload_deliver();
+    if (e == hipSuccess) e = preload_tracker();
     return e;
 }
 

@@ -120,6 +120,13 @@ __global__ __launch_bounds__(64) void outbound_step_kernel(const outb::Ctx c) {
     }
 }
 
+// srt_outbound_cached_seq: one thread a host
+__global__ __launch_bounds__(256) void outbound_cached_seq_kernel(const outb::Host *__restrict__ hosts, uint32_t n_hosts,
+                                                                  uint64_t *__restrict__ seq) {
+    const uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h < n_hosts) seq[h] = outb::cached_seq_of(hosts[h]);
+}
+
 void set_err(srt_err *err, srt_status code, const char *msg) {
     if (!err) return;
     err->code = code;
@@ -419,6 +426,27 @@ extern "C" srt_status srt_outbound_state(srt_outbound *ob, srt_outbound_host_sta
         o.queue_len = s.ring_len;
         o.cached = s.cached;
         o.overflow = s.overflow;
+    }
+    return SRT_OK;
+}
+
+extern "C" srt_status srt_outbound_cached_seq(srt_outbound *ob, uint64_t *d_seq, srt_err *err) {
+    if (err) std::memset(err, 0, sizeof *err);
+    if (!ob || (ob->n && !d_seq)) {
+        set_err(err, SRT_ERR_INVALID, "null argument");
+        return SRT_ERR_INVALID;
+    }
+    if (!ob->n) return SRT_OK;
+    if (!ob->plan) {
+        for (uint32_t h = 0; h < ob->n; ++h) d_seq[h] = outb::cached_seq_of(ob->hosts[h]);
+        return SRT_OK;
+    }
+    if (hipSetDevice(ob->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    hipLaunchKernelGGL(outbound_cached_seq_kernel, dim3((ob->n + 255) / 256), dim3(256), 0, ob->plan->stream, ob->hosts,
+                       ob->n, d_seq);
+    if (hipGetLastError() != hipSuccess) {
+        set_err(err, SRT_ERR_HIP, "outbound: launch failed");
+        return SRT_ERR_HIP;
     }
     return SRT_OK;
 }

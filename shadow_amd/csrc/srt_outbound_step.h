@@ -102,6 +102,9 @@ struct alignas(16) Host {
     uint32_t pad[2];
 };
 
+// the seq of the packet the relay holds cached between calls (srt_outbound_cached_seq)
+SRT_HD uint64_t cached_seq_of(const Host &s) { return s.cached ? s.cached_seq : NONE; }
+
 struct Ctx {
     Host *hosts;
     RingEl *ring;

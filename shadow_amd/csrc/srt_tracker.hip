@@ -1,0 +1,521 @@
+// srt_tracker.hip -- the tracker's heartbeat byte counters of the internet
+// interface (host/tracker.c:188-284, 582-627): per host and per socket slot, in
+// and out, what tracker_addOutputBytes adds in networkinterface_pop and
+// tracker_addInputBytes in networkinterface_push, kept on the device between
+// heartbeats.  The step -- the classes, the pop-time rule of the output side,
+// the note ring and seq log rules, the range checks -- is srt_tracker_step.h,
+// compiled here for the device and for the host-only instance alike.
+//
+// Device form, on the plan's stream; only heartbeat and status wait for it.
+//   note: one launch, a copy of the round's metas into the ring.
+//   tx, two launches (one without a late list):
+//     (1) late: one thread a late record (grid-stride): the remembered seq of
+//         its host, the log, 64-bit atomics on the host's record and the slot's;
+//     (2) hosts: a group of L lanes owns one source host and walks its segment
+//         of d_status / d_meta with coalesced loads; every lane keeps the ten
+//         sums of its packets in registers, a popped packet adds to its socket
+//         slot with two or three 64-bit atomics, a packet that stays queued has
+//         its meta written to the seq log.  The group's first lane takes the
+//         host's cached packet (rules 3 and 4), the sums are reduced across
+//         the group's lanes and that lane adds them to the host's record with
+//         ordinary loads and stores: no other lane of the launch has that
+//         record.  L is 64 (a wave a host) when the batch averages more than
+//         16 packets a host, else 8 (eight hosts a wave).
+//   rx: one launch of the same geometry over srt_deliver_run's list, bounded by
+//       min(d_out_host_ptr[n_hosts], out_cap) on the device; L from out_cap.
+//   rx_flat: one thread a record, atomics on the host's record and the slot's.
+// The launches of one stream run in order, so a record's atomic adds (late,
+// flat) and its plain read-modify-write (the hosts' walk) never overlap.  No
+// kernel adds to a call-wide counter: the packets counted are kept a host and
+// srt_tracker_status, which synchronises anyway, sums them with one launch.
+// Every value is written with ordinary stores or vector atomics from plain C++.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "srt_internal.h"
+#include "srt_tracker_step.h"
+
+namespace {
+
+static_assert(sizeof(srt_trk_counters) == 80 && sizeof(srt_trk_meta) == 16 && sizeof(tracker::State) == 24 &&
+                  sizeof(srt_outbound_late) == 32,
+              "record layouts");
+
+constexpr uint32_t BT = 256;            // threads a workgroup
+constexpr uint32_t ST = 1024;           // threads of the status sum's one workgroup
+constexpr uint32_t LATE_BLOCKS = 1024;  // at most, each striding over the late list or the flat records
+constexpr uint32_t NOTE_BLOCKS = 4096;  // at most, each striding over the note
+constexpr uint32_t WIDE_AVG = 16;       // more packets a host on average: a wave a host
+
+// the sums of the group's L lanes, in every one of them
+template <uint32_t L>
+__device__ __forceinline__ void group_sum(tracker::Acc &a) {
+#pragma unroll
+    for (uint32_t j = 0; j < tracker::N_CTR; ++j) {
+        unsigned long long v = a.v[j];
+#pragma unroll
+        for (uint32_t off = L / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        a.v[j] = v;
+    }
+}
+
+__global__ __launch_bounds__(BT) void tracker_note_kernel(const tracker::Ctx c) {
+    for (uint64_t i = (uint64_t)c.note_first + (uint64_t)blockIdx.x * BT + threadIdx.x; i < c.note_n;
+         i += (uint64_t)gridDim.x * BT)
+        tracker::note_store(c, (uint32_t)i);
+}
+
+__global__ __launch_bounds__(BT) void tracker_late_kernel(const tracker::Ctx c) {
+    const uint32_t n = tracker::late_n(c);
+    for (uint64_t k = (uint64_t)blockIdx.x * BT + threadIdx.x; k < n; k += (uint64_t)gridDim.x * BT)
+        tracker::tx_late(c, (uint32_t)k);
+}
+
+template <uint32_t L>
+__global__ __launch_bounds__(BT) void tracker_tx_kernel(const tracker::Ctx c) {
+    const uint64_t g = ((uint64_t)blockIdx.x * BT + threadIdx.x) / L;
+    const uint32_t l = threadIdx.x % L;
+    const bool own = g < c.n_hosts;
+    tracker::Acc a;
+    tracker::acc_zero(a);
+    if (own) {
+        uint32_t b, e;
+        tracker::segment(c.host_ptr, tracker::tx_walked(c), (uint32_t)g, b, e);
+        for (uint32_t i = b + l; i < e; i += L) tracker::tx_batch(c, i, a);
+        if (l == 0) tracker::tx_cached(c, (uint32_t)g, a);
+    }
+    group_sum<L>(a);  // every lane is here
+    if (own && l == 0) tracker::host_merge(c.node_out + g, c.cnt_tx + g, a);
+}
+
+template <uint32_t L>
+__global__ __launch_bounds__(BT) void tracker_rx_kernel(const tracker::Ctx c) {
+    const uint64_t g = ((uint64_t)blockIdx.x * BT + threadIdx.x) / L;
+    const uint32_t l = threadIdx.x % L;
+    const bool own = g < c.n_hosts;
+    tracker::Acc a;
+    tracker::acc_zero(a);
+    if (own) {
+        uint32_t b, e;
+        tracker::segment(c.out_host_ptr, tracker::rx_walked(c), (uint32_t)g, b, e);
+        for (uint32_t p = b + l; p < e; p += L) tracker::rx_record(c, p, a);
+    }
+    group_sum<L>(a);
+    if (own && l == 0) tracker::host_merge(c.node_in + g, c.cnt_rx + g, a);
+}
+
+__global__ __launch_bounds__(BT) void tracker_flat_kernel(const tracker::Ctx c) {
+    for (uint64_t k = (uint64_t)blockIdx.x * BT + threadIdx.x; k < c.f_n; k += (uint64_t)gridDim.x * BT)
+        tracker::rx_flat(c, (uint32_t)k);
+}
+
+// srt_tracker_status: the hosts' counts of packets, summed by one workgroup
+__global__ __launch_bounds__(ST) void tracker_sum_kernel(const tracker::Ctx c) {
+    __shared__ uint64_t wsum[2][ST / 64];
+    const uint32_t t = threadIdx.x;
+    unsigned long long tx = 0, rx = 0;
+    for (uint32_t h = t; h < c.n_hosts; h += ST) tx += c.cnt_tx[h], rx += c.cnt_rx[h];
+    for (uint32_t off = 32; off > 0; off >>= 1) tx += __shfl_xor(tx, off), rx += __shfl_xor(rx, off);
+    if ((t & 63) == 0) wsum[0][t >> 6] = tx, wsum[1][t >> 6] = rx;
+    __syncthreads();
+    if (t == 0) {
+        uint64_t a = 0, b = 0;
+        for (uint32_t w = 0; w < ST / 64; ++w) a += wsum[0][w], b += wsum[1][w];
+        c.st->n_tx = a;
+        c.st->n_rx = b;
+    }
+}
+
+void set_err(srt_err *err, srt_status code, const char *msg) {
+    if (!err) return;
+    err->code = code;
+    std::snprintf(err->msg, sizeof err->msg, "%s", msg);
+}
+
+}  // namespace
+
+struct srt_tracker {
+    srt_plan *plan = nullptr;  // nullptr: host-only
+    uint32_t n_hosts = 0, n_sockets = 0;
+    uint64_t note_cap = 0, log_cap = 0;
+    uint64_t note_end = 0;
+    void *mem = nullptr;  // device form: everything in one allocation; host-only: h_mem
+    size_t rec_bytes = 0;  // the four record arrays, contiguous from node_in
+    std::vector<uint64_t> h_mem;
+    std::vector<srt_trk_counters> stage;  // device form: the records on the host, for the heartbeat
+    tracker::Ctx base;
+};
+
+namespace srt {
+// srt_init: loads this unit's code object (srt::preload_kernels)
+hipError_t preload_tracker() {
+    hipFuncAttributes a;
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&tracker_sum_kernel));
+}
+}  // namespace srt
+
+extern "C" void srt_tracker_destroy(srt_tracker *trk) {
+    if (!trk) return;
+    if (trk->plan) {
+        (void)hipSetDevice(trk->plan->device);
+        (void)hipStreamSynchronize(trk->plan->stream);
+        (void)hipFree(trk->mem);
+    }
+    delete trk;
+}
+
+extern "C" srt_status srt_tracker_create(srt_plan *plan, uint32_t n_hosts, uint32_t n_sockets, uint64_t note_cap,
+                                         uint64_t log_cap, srt_tracker **out, srt_err *err) {
+    if (err) std::memset(err, 0, sizeof *err);
+    if (!out) {
+        set_err(err, SRT_ERR_INVALID, "null argument");
+        return SRT_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (n_hosts >= 0x80000000u || n_sockets >= 0x80000000u || note_cap > (1ull << 31) || log_cap > (1ull << 31)) {
+        set_err(err, SRT_ERR_INVALID,
+                "tracker: n_hosts, n_sockets (below 2^31), note_cap or log_cap (at most 2^31) out of range");
+        return SRT_ERR_INVALID;
+    }
+    srt_tracker *trk = new (std::nothrow) srt_tracker;
+    if (!trk) return SRT_ERR_OOM;
+    trk->plan = plan;
+    trk->n_hosts = n_hosts;
+    trk->n_sockets = n_sockets;
+    trk->note_cap = note_cap;
+    trk->log_cap = log_cap;
+    // state; the hosts' and the slots' records; the ring; the log; the hosts' counts and remembered seqs
+    const size_t head = 32, recs = 2 * ((size_t)n_hosts + n_sockets);
+    trk->rec_bytes = recs * sizeof(srt_trk_counters);
+    const size_t words = 24 * (size_t)n_hosts, bytes = head + trk->rec_bytes + words + 16 * (size_t)(note_cap + log_cap);
+    bool ok = true;
+    if (!plan) {
+        try {
+            trk->h_mem.assign(bytes / 8 + 1, 0);
+        } catch (const std::bad_alloc &) {
+            ok = false;
+        }
+        trk->mem = trk->h_mem.data();
+    } else {
+        try {
+            trk->stage.resize(recs + 1);
+        } catch (const std::bad_alloc &) {
+            ok = false;
+        }
+        if (ok) {
+            srt::init_wait();
+            ok = hipSetDevice(plan->device) == hipSuccess;
+            ok = ok && hipMalloc(&trk->mem, bytes + 8) == hipSuccess;
+            ok = ok && hipMemset(trk->mem, 0, bytes + 8) == hipSuccess;
+            if (!ok) {
+                (void)hipGetLastError();
+                (void)hipFree(trk->mem);
+            }
+        }
+    }
+    if (!ok) {
+        delete trk;
+        set_err(err, SRT_ERR_OOM, "tracker: allocation failed");
+        return SRT_ERR_OOM;
+    }
+    tracker::Ctx &c = trk->base;
+    std::memset(&c, 0, sizeof c);
+    char *p = static_cast<char *>(trk->mem);
+    c.st = reinterpret_cast<tracker::State *>(p);
+    c.node_in = reinterpret_cast<srt_trk_counters *>(p + head);
+    c.node_out = c.node_in + n_hosts;
+    c.sock_in = c.node_out + n_hosts;
+    c.sock_out = c.sock_in + n_sockets;
+    c.ring = reinterpret_cast<srt_trk_meta *>(p + head + trk->rec_bytes);  // 16-byte aligned
+    c.log = c.ring + note_cap;
+    c.cnt_tx = reinterpret_cast<uint64_t *>(c.log + log_cap);
+    c.cnt_rx = c.cnt_tx + n_hosts;
+    c.remembered = c.cnt_rx + n_hosts;
+    c.n_hosts = n_hosts;
+    c.n_sockets = n_sockets;
+    c.note_cap = note_cap;
+    c.log_cap = log_cap;
+    // no host holds a cached packet yet
+    if (!plan) {
+        for (uint32_t h = 0; h < n_hosts; ++h) c.remembered[h] = tracker::NONE;
+    } else if (n_hosts && hipMemset(c.remembered, 0xff, 8 * (size_t)n_hosts) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(trk->mem);
+        delete trk;
+        set_err(err, SRT_ERR_HIP, "tracker: device initialisation failed");
+        return SRT_ERR_HIP;
+    }
+    *out = trk;
+    return SRT_OK;
+}
+
+namespace {
+srt_status launched(srt_err *err) {
+    if (hipGetLastError() != hipSuccess) {
+        set_err(err, SRT_ERR_HIP, "tracker: launch failed");
+        return SRT_ERR_HIP;
+    }
+    return SRT_OK;
+}
+
+// blocks of the hosts' walk: BT / L hosts each
+uint32_t host_blocks(uint32_t n_hosts, bool wide) {
+    const uint32_t per = wide ? BT / 64 : BT / 8;
+    return (uint32_t)(((uint64_t)n_hosts + per - 1) / per);
+}
+}  // namespace
+
+extern "C" srt_status srt_tracker_tx(srt_tracker *trk, const uint64_t *d_cached_seq, const uint32_t *d_host_ptr,
+                                     uint64_t n_pkts, const srt_trk_meta *d_meta, const uint32_t *d_status,
+                                     uint64_t seq_base, const srt_outbound_late *d_late, uint32_t late_cap,
+                                     const uint32_t *d_late_count, srt_err *err) {
+    if (err) std::memset(err, 0, sizeof *err);
+    if (!trk || !d_host_ptr || (trk->n_hosts && !d_cached_seq) || (n_pkts && (!d_meta || !d_status)) ||
+        (late_cap && (!d_late || !d_late_count))) {
+        set_err(err, SRT_ERR_INVALID, "null argument");
+        return SRT_ERR_INVALID;
+    }
+    if (n_pkts >= 0x80000000ull || late_cap >= 0x80000000u || seq_base + n_pkts < seq_base) {
+        set_err(err, SRT_ERR_INVALID, "more than 2^31-1 packets in one batch or late list");
+        return SRT_ERR_INVALID;
+    }
+    tracker::Ctx c = trk->base;
+    c.base_mod = trk->log_cap ? seq_base % trk->log_cap : 0;
+    c.end_mod = trk->log_cap ? (seq_base + n_pkts) % trk->log_cap : 0;
+    c.cached_seq = d_cached_seq;
+    c.host_ptr = d_host_ptr;
+    c.status = d_status;
+    c.meta = d_meta;
+    c.late = d_late;
+    c.late_count = late_cap ? d_late_count : nullptr;
+    c.late_cap = late_cap;
+    c.seq_base = seq_base;
+    c.n_pkts = (uint32_t)n_pkts;
+    if (!trk->plan) {
+        tracker::host_tx(c);
+        return SRT_OK;
+    }
+    if (hipSetDevice(trk->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    hipStream_t s = trk->plan->stream;
+    if (late_cap)
+        hipLaunchKernelGGL(tracker_late_kernel, dim3(std::min<uint32_t>((late_cap + BT - 1) / BT, LATE_BLOCKS)),
+                           dim3(BT), 0, s, c);
+    if (c.n_hosts) {
+        const bool wide = n_pkts > (uint64_t)WIDE_AVG * c.n_hosts;
+        if (wide) hipLaunchKernelGGL(tracker_tx_kernel<64>, dim3(host_blocks(c.n_hosts, true)), dim3(BT), 0, s, c);
+        else hipLaunchKernelGGL(tracker_tx_kernel<8>, dim3(host_blocks(c.n_hosts, false)), dim3(BT), 0, s, c);
+    }
+    return launched(err);
+}
+
+extern "C" srt_status srt_tracker_note(srt_tracker *trk, const srt_trk_meta *d_meta, uint64_t n_pkts,
+                                       uint64_t tag_base, srt_err *err) {
+    if (err) std::memset(err, 0, sizeof *err);
+    if (!trk || (n_pkts && !d_meta)) {
+        set_err(err, SRT_ERR_INVALID, "null argument");
+        return SRT_ERR_INVALID;
+    }
+    if (n_pkts >= 0x80000000ull || tag_base < trk->note_end || tag_base + n_pkts < tag_base) {
+        set_err(err, SRT_ERR_INVALID, "tracker: more than 2^31-1 packets in one note, or tag_base below the previous note's end");
+        return SRT_ERR_INVALID;
+    }
+    trk->note_end = tag_base + n_pkts;
+    if (!n_pkts || !trk->note_cap) return SRT_OK;
+    tracker::Ctx c = trk->base;
+    c.note_in = d_meta;
+    c.note_n = (uint32_t)n_pkts;
+    c.note_first = n_pkts > trk->note_cap ? (uint32_t)(n_pkts - trk->note_cap) : 0u;
+    c.note_first_mod = (tag_base + c.note_first) % trk->note_cap;
+    if (!trk->plan) {
+        tracker::host_note(c);
+        return SRT_OK;
+    }
+    if (hipSetDevice(trk->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_pkts - c.note_first + BT - 1) / BT, NOTE_BLOCKS);
+    hipLaunchKernelGGL(tracker_note_kernel, dim3(blocks), dim3(BT), 0, trk->plan->stream, c);
+    return launched(err);
+}
+
+extern "C" srt_status srt_tracker_rx(srt_tracker *trk, const uint32_t *d_out_host_ptr, const uint32_t *d_out_socket,
+                                     const uint64_t *d_out_tag, const uint32_t *d_out_status, uint64_t out_cap,
+                                     srt_err *err) {
+    if (err) std::memset(err, 0, sizeof *err);
+    if (!trk || !d_out_host_ptr || (out_cap && (!d_out_socket || !d_out_tag || !d_out_status))) {
+        set_err(err, SRT_ERR_INVALID, "null argument");
+        return SRT_ERR_INVALID;
+    }
+    tracker::Ctx c = trk->base;
+    c.note_end = trk->note_end;
+    c.note_end_mod = trk->note_cap ? trk->note_end % trk->note_cap : 0;
+    c.out_host_ptr = d_out_host_ptr;
+    c.out_socket = d_out_socket;
+    c.out_tag = d_out_tag;
+    c.out_status = d_out_status;
+    c.out_cap = out_cap < 0xffffffffull ? out_cap : 0xffffffffull;  // positions are u32
+    if (!trk->plan) {
+        tracker::host_rx(c);
+        return SRT_OK;
+    }
+    if (!c.n_hosts) return SRT_OK;
+    if (hipSetDevice(trk->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    hipStream_t s = trk->plan->stream;
+    const bool wide = out_cap > (uint64_t)WIDE_AVG * c.n_hosts;
+    if (wide) hipLaunchKernelGGL(tracker_rx_kernel<64>, dim3(host_blocks(c.n_hosts, true)), dim3(BT), 0, s, c);
+    else hipLaunchKernelGGL(tracker_rx_kernel<8>, dim3(host_blocks(c.n_hosts, false)), dim3(BT), 0, s, c);
+    return launched(err);
+}
+
+extern "C" srt_status srt_tracker_rx_flat(srt_tracker *trk, const uint32_t *d_host, const uint32_t *d_socket,
+                                          const srt_trk_meta *d_meta, uint64_t n, srt_err *err) {
+    if (err) std::memset(err, 0, sizeof *err);
+    if (!trk || (n && (!d_host || !d_socket || !d_meta))) {
+        set_err(err, SRT_ERR_INVALID, "null argument");
+        return SRT_ERR_INVALID;
+    }
+    if (n >= 0x80000000ull) {
+        set_err(err, SRT_ERR_INVALID, "more than 2^31-1 records in one call");
+        return SRT_ERR_INVALID;
+    }
+    if (!n) return SRT_OK;
+    tracker::Ctx c = trk->base;
+    c.f_host = d_host;
+    c.f_socket = d_socket;
+    c.f_meta = d_meta;
+    c.f_n = (uint32_t)n;
+    if (!trk->plan) {
+        tracker::host_rx_flat(c);
+        return SRT_OK;
+    }
+    if (hipSetDevice(trk->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    hipLaunchKernelGGL(tracker_flat_kernel, dim3((uint32_t)std::min<uint64_t>((n + BT - 1) / BT, LATE_BLOCKS)), dim3(BT),
+                       0, trk->plan->stream, c);
+    return launched(err);
+}
+
+extern "C" srt_status srt_tracker_heartbeat(srt_tracker *trk, const uint32_t *hosts, uint32_t n_sel_hosts,
+                                            const uint32_t *sockets, uint32_t n_sel_sockets,
+                                            srt_trk_counters *out_node_in, srt_trk_counters *out_node_out,
+                                            srt_trk_counters *out_sock_in, srt_trk_counters *out_sock_out,
+                                            srt_err *err) {
+    if (err) std::memset(err, 0, sizeof *err);
+    if (!trk) {
+        set_err(err, SRT_ERR_INVALID, "null argument");
+        return SRT_ERR_INVALID;
+    }
+    const uint32_t nh = hosts ? n_sel_hosts : trk->n_hosts, ns = sockets ? n_sel_sockets : trk->n_sockets;
+    for (uint32_t k = 0; hosts && k < nh; ++k)
+        if (hosts[k] >= trk->n_hosts) {
+            set_err(err, SRT_ERR_INVALID, "tracker: a selected host is not below n_hosts (nothing was cleared)");
+            return SRT_ERR_INVALID;
+        }
+    for (uint32_t k = 0; sockets && k < ns; ++k)
+        if (sockets[k] >= trk->n_sockets) {
+            set_err(err, SRT_ERR_INVALID, "tracker: a selected socket slot is not below n_sockets (nothing was cleared)");
+            return SRT_ERR_INVALID;
+        }
+    // the four record arrays as the host sees them: the instance's own memory, or the staged copy
+    srt_trk_counters *recs = trk->base.node_in;
+    const bool all = !hosts && !sockets;
+    if (trk->plan) {
+        if (hipSetDevice(trk->plan->device) != hipSuccess) return SRT_ERR_HIP;
+        hipStream_t s = trk->plan->stream;
+        recs = trk->stage.data();
+        if ((trk->rec_bytes &&
+             hipMemcpyAsync(recs, trk->base.node_in, trk->rec_bytes, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            (void)hipGetLastError();
+            set_err(err, SRT_ERR_HIP, "tracker: stream failed");
+            return SRT_ERR_HIP;
+        }
+    }
+    srt_trk_counters *node_in = recs, *node_out = node_in + trk->n_hosts, *sock_in = node_out + trk->n_hosts,
+                     *sock_out = sock_in + trk->n_sockets;
+    for (uint32_t k = 0; k < nh; ++k) {
+        const uint32_t h = hosts ? hosts[k] : k;
+        if (out_node_in) out_node_in[k] = node_in[h];
+        if (out_node_out) out_node_out[k] = node_out[h];
+    }
+    for (uint32_t k = 0; k < ns; ++k) {
+        const uint32_t x = sockets ? sockets[k] : k;
+        if (out_sock_in) out_sock_in[k] = sock_in[x];
+        if (out_sock_out) out_sock_out[k] = sock_out[x];
+    }
+    // tracker.c:607-619: the selected records start the next interval at zero
+    const srt_trk_counters zero = {};
+    for (uint32_t k = 0; k < nh; ++k) node_in[hosts ? hosts[k] : k] = node_out[hosts ? hosts[k] : k] = zero;
+    for (uint32_t k = 0; k < ns; ++k) sock_in[sockets ? sockets[k] : k] = sock_out[sockets ? sockets[k] : k] = zero;
+    if (trk->plan && trk->rec_bytes && (nh || ns)) {
+        // the stream is idle: the cleared copy goes back whole (everything selected: a memset)
+        hipStream_t s = trk->plan->stream;
+        const hipError_t e = all ? hipMemsetAsync(trk->base.node_in, 0, trk->rec_bytes, s)
+                                 : hipMemcpyAsync(trk->base.node_in, recs, trk->rec_bytes, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+            (void)hipGetLastError();
+            set_err(err, SRT_ERR_HIP, "tracker: clearing the records failed");
+            return SRT_ERR_HIP;
+        }
+    }
+    return SRT_OK;
+}
+
+extern "C" srt_status srt_tracker_status(srt_tracker *trk, uint32_t *flags, uint64_t *n_tx_counted,
+                                         uint64_t *n_rx_counted, srt_err *err) {
+    if (err) std::memset(err, 0, sizeof *err);
+    if (!trk) {
+        set_err(err, SRT_ERR_INVALID, "null argument");
+        return SRT_ERR_INVALID;
+    }
+    tracker::State w;
+    if (!trk->plan) {
+        const tracker::Ctx &c = trk->base;
+        c.st->n_tx = c.st->n_rx = 0;
+        for (uint32_t h = 0; h < c.n_hosts; ++h) c.st->n_tx += c.cnt_tx[h], c.st->n_rx += c.cnt_rx[h];
+        w = *c.st;
+        c.st->flags = 0;
+    } else {
+        if (hipSetDevice(trk->plan->device) != hipSuccess) return SRT_ERR_HIP;
+        hipStream_t s = trk->plan->stream;
+        hipLaunchKernelGGL(tracker_sum_kernel, dim3(1), dim3(ST), 0, s, trk->base);
+        if (hipMemcpyAsync(&w, trk->base.st, sizeof w, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            (void)hipGetLastError();
+            set_err(err, SRT_ERR_HIP, "tracker: stream failed");
+            return SRT_ERR_HIP;
+        }
+        if (w.flags) (void)hipMemsetAsync(&trk->base.st->flags, 0, 4, s);
+    }
+    const uint32_t f = w.flags & 15u;
+    if (flags) *flags = f;
+    if (n_tx_counted) *n_tx_counted = w.n_tx;
+    if (n_rx_counted) *n_rx_counted = w.n_rx;
+    if (!f) return SRT_OK;
+    if (err) {
+        err->code = SRT_ERR_INVALID;
+        std::snprintf(err->msg, sizeof err->msg, "tracker:%s%s%s%s",
+                      f & tracker::F_LOG_OVERRUN ? " a late or cached packet's seq is older than the log holds (not counted);" : "",
+                      f & tracker::F_NOTE_OVERRUN ? " a placeholder record or a tag the note ring does not hold (skipped);" : "",
+                      f & tracker::F_BAD_SOCKET ? " a socket slot is not below n_sockets (counted at its host only);" : "",
+                      f & tracker::F_BAD_HOST ? " a record's host is not below n_hosts (skipped);" : "");
+    }
+    return SRT_ERR_INVALID;
+}
+
+extern "C" int srt_tracker_counter_string(const srt_trk_counters *c, char *buf, size_t cap) {
+    if (!c || (cap && !buf)) return -1;
+    const unsigned long long packets =
+        c->packets_control + c->packets_control_retrans + c->packets_data + c->packets_data_retrans;
+    const unsigned long long bytes = c->bytes_control_header + c->bytes_control_header_retrans + c->bytes_data_header +
+                                     c->bytes_data_header_retrans + c->bytes_data_payload +
+                                     c->bytes_data_payload_retrans;
+    return std::snprintf(buf, cap, "%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu,%llu", packets, bytes,
+                         (unsigned long long)c->packets_control, (unsigned long long)c->bytes_control_header,
+                         (unsigned long long)c->packets_control_retrans,
+                         (unsigned long long)c->bytes_control_header_retrans, (unsigned long long)c->packets_data,
+                         (unsigned long long)c->bytes_data_header, (unsigned long long)c->bytes_data_payload,
+                         (unsigned long long)c->packets_data_retrans, (unsigned long long)c->bytes_data_header_retrans,
+                         (unsigned long long)c->bytes_data_payload_retrans);
+}

@@ -429,6 +429,19 @@ class OutboundRelay:
             self._h, out.ctypes.data_as(C.POINTER(_lib.SrtOutboundHostState)), C.byref(err)), err)
         return out
 
+    def cached_seq(self, out):
+        """srt_outbound_cached_seq: out int64/uint64 [n_hosts] receives the seq of the
+        packet every host's relay holds cached after the last run, or UINT64_MAX.
+        Device form: enqueue only."""
+        if SendBatch._nbytes(out) < 8 * self.n_hosts:
+            raise ValueError("OutboundRelay.cached_seq: out is smaller than n_hosts")
+        cur, ps = FlightStore._streams(self, out) if self.n_hosts else (None, None)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_outbound_cached_seq(self._h, self._ptr(out), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)
+        return out
+
     def close(self):
         if self._h:
             _lib.lib().srt_outbound_destroy(self._h)
@@ -751,6 +764,159 @@ class DeliverStage:
     def close(self):
         if self._h:
             _lib.lib().srt_deliver_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+TRK_META_DTYPE = np.dtype([("header_size", "<u4"), ("payload_size", "<u4"), ("flags", "<u4"), ("socket_slot", "<u4")])
+TRK_COUNTER_FIELDS = ("packets_control", "bytes_control_header", "packets_control_retrans",
+                      "bytes_control_header_retrans", "packets_data", "bytes_data_header", "bytes_data_payload",
+                      "packets_data_retrans", "bytes_data_header_retrans", "bytes_data_payload_retrans")
+TRK_COUNTERS_DTYPE = np.dtype([(k, "<u8") for k in TRK_COUNTER_FIELDS])
+
+
+class Tracker:
+    """srt_tracker: the tracker's heartbeat byte counters of the internet
+    interface (host/tracker.c), per host and per socket slot, in and out,
+    kept where the pipeline runs: tx() counts what the interface popped in
+    the OutboundRelay.run call just made, note() stores a round's
+    TRK_META_DTYPE records under the flight tags of the round's push, rx()
+    counts DeliverStage.run's list, rx_flat() ungrouped records, heartbeat()
+    returns and clears the selected records (TRK_COUNTERS_DTYPE).
+
+    Bound to a RoutingPlan (arrays are torch CUDA tensors of its device, the
+    calls are asynchronous on its stream; closing the plan closes it), or
+    host-only with plan=None (arrays are numpy arrays, the same step on the
+    CPU)."""
+
+    def __init__(self, plan: Optional[RoutingPlan], n_hosts: int, n_sockets: int, note_cap: int, log_cap: int):
+        self.plan = plan
+        self.n_hosts, self.n_sockets = int(n_hosts), int(n_sockets)
+        self._h = C.c_void_p()
+        if plan is not None:
+            _bind_to_plan(self, plan)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_tracker_create(plan.handle if plan is not None else None, self.n_hosts,
+                                                 self.n_sockets, int(note_cap), int(log_cap), C.byref(self._h),
+                                                 C.byref(err)), err)
+
+    _ptr = staticmethod(InboundRouter._ptr)
+    _nbytes = staticmethod(SendBatch._nbytes)
+    _streams = FlightStore._streams
+
+    def tx(self, cached_seq, host_ptr, meta, status, seq_base: int, late=None, late_count=None):
+        """srt_tracker_tx on the arrays of the OutboundRelay.run call just made:
+        cached_seq int64/uint64 [n_hosts] as OutboundRelay.cached_seq wrote it
+        after that call, host_ptr int32/uint32 [n_hosts+1], meta a uint8 view of
+        16-byte srt_trk_meta records, one a batch packet, status int32/uint32
+        (its size is n_pkts), the run's return value as seq_base, late (a uint8
+        buffer of 32-byte records) and late_count.  Device form: enqueue only."""
+        n_pkts = self._nbytes(status) // 4
+        late_cap = self._nbytes(late) // 32
+        if self._nbytes(cached_seq) < 8 * self.n_hosts or self._nbytes(host_ptr) < 4 * (self.n_hosts + 1) or \
+                self._nbytes(meta) < 16 * n_pkts or (late_cap and late_count is None):
+            raise ValueError("Tracker.tx: an array is smaller than its record count")
+        cur, ps = self._streams(host_ptr)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_tracker_tx(
+            self._h, self._ptr(cached_seq), self._ptr(host_ptr), n_pkts, self._ptr(meta), self._ptr(status),
+            int(seq_base), self._ptr(late), late_cap, self._ptr(late_count), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)
+
+    def note(self, meta, tag_base: int):
+        """srt_tracker_note after FlightStore.push (tag=None) of a round: meta, a
+        uint8 view of the round's 16-byte srt_trk_meta records, one a batch
+        packet; tag_base as the push returned it."""
+        n_pkts = self._nbytes(meta) // 16
+        cur, ps = self._streams(meta) if n_pkts else (None, None)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_tracker_note(self._h, self._ptr(meta), n_pkts, int(tag_base), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)
+
+    def rx(self, out_host_ptr, out_socket, out_tag, out_status):
+        """srt_tracker_rx on DeliverStage.run's outputs as they are: out_host_ptr
+        int32/uint32 [n_hosts+1], out_socket int32/uint32 (its size is
+        out_cap), out_tag int64/uint64 and out_status int32/uint32 [out_cap].
+        Device form: enqueue only; nothing is read back."""
+        out_cap = self._nbytes(out_socket) // 4
+        if self._nbytes(out_host_ptr) < 4 * (self.n_hosts + 1) or self._nbytes(out_tag) < 8 * out_cap or \
+                self._nbytes(out_status) < 4 * out_cap:
+            raise ValueError("Tracker.rx: an array is smaller than its record count")
+        cur, ps = self._streams(out_host_ptr)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_tracker_rx(self._h, self._ptr(out_host_ptr), self._ptr(out_socket),
+                                             self._ptr(out_tag), self._ptr(out_status), out_cap, C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)
+
+    def rx_flat(self, host, socket, meta):
+        """srt_tracker_rx_flat: host and socket int32/uint32 [n], meta a uint8
+        view of n 16-byte srt_trk_meta records."""
+        n = self._nbytes(host) // 4
+        if self._nbytes(socket) < 4 * n or self._nbytes(meta) < 16 * n:
+            raise ValueError("Tracker.rx_flat: an array is smaller than its record count")
+        cur, ps = self._streams(host) if n else (None, None)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_tracker_rx_flat(self._h, self._ptr(host), self._ptr(socket), self._ptr(meta), n,
+                                                  C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)
+
+    def heartbeat(self, hosts=None, sockets=None):
+        """srt_tracker_heartbeat: synchronises; returns (node_in, node_out,
+        sock_in, sock_out), TRK_COUNTERS_DTYPE record arrays for the selected
+        hosts and socket slots (None: all; an empty list: none), and clears
+        exactly those records."""
+        def sel(x, n_all):
+            if x is None:
+                return None, n_all
+            a = np.ascontiguousarray(x, np.uint32).reshape(-1)
+            if not len(a):
+                a = np.zeros(1, np.uint32)  # a selection of none: a non-NULL pointer, count 0
+                return a, 0
+            return a, len(a)
+
+        hs, nh = sel(hosts, self.n_hosts)
+        ss, ns = sel(sockets, self.n_sockets)
+        outs = [np.zeros(nh, TRK_COUNTERS_DTYPE), np.zeros(nh, TRK_COUNTERS_DTYPE),
+                np.zeros(ns, TRK_COUNTERS_DTYPE), np.zeros(ns, TRK_COUNTERS_DTYPE)]
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_tracker_heartbeat(
+            self._h, None if hs is None else hs.ctypes.data, nh, None if ss is None else ss.ctypes.data, ns,
+            *[o.ctypes.data if len(o) else None for o in outs], C.byref(err)), err)
+        return tuple(outs)
+
+    def status(self, check: bool = True):
+        """srt_tracker_status: synchronises; (flags, packets counted on the
+        output side since create, on the input side).  check=True raises
+        SrtError when a flag is set."""
+        flags, a, b = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        err = _lib.SrtErr()
+        rc = _lib.lib().srt_tracker_status(self._h, C.byref(flags), C.byref(a), C.byref(b), C.byref(err))
+        if check or (rc != _lib.SRT_OK and not flags.value):
+            _lib.check(rc, err)
+        return flags.value, a.value, b.value
+
+    @staticmethod
+    def counter_string(rec) -> str:
+        """srt_tracker_counter_string: the twelve comma-separated numbers of a
+        heartbeat line for one TRK_COUNTERS_DTYPE record."""
+        r = np.ascontiguousarray(rec, TRK_COUNTERS_DTYPE).reshape(-1)[:1].copy()
+        buf = C.create_string_buffer(256)
+        if _lib.lib().srt_tracker_counter_string(r.ctypes.data, buf, 256) < 0:
+            raise ValueError("Tracker.counter_string: bad record")
+        return buf.value.decode()
+
+    def close(self):
+        if self._h:
+            _lib.lib().srt_tracker_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
