@@ -614,6 +614,17 @@ srt_status srt_deliver_disassociate(srt_deliver *dl, const srt_assoc *assoc, uin
 srt_status srt_deliver_lookup(srt_deliver *dl, const uint32_t *hosts, const srt_rx_meta *meta, uint64_t n,
                               uint32_t *sockets, srt_err *err);
 
+/* The same lookup for n (< 2^31) records in device arrays, asynchronous on the
+ * plan's stream: the table is uploaded first if the associations have changed
+ * since the last upload, as srt_deliver_run does it, then one thread a record
+ * probes it.  A host >= n_hosts gives UINT32_MAX.  On a host-only instance it
+ * is srt_deliver_lookup.  With it the SRT_OUT_LOCAL packets of an outbound
+ * call go to srt_tracker_rx_flat without a read-back.  KNOWN GAP: the order of
+ * those packets among themselves stays the caller's; srt_outbound_run returns
+ * their send time and no rank. */
+srt_status srt_deliver_lookup_flat(srt_deliver *dl, const uint32_t *d_hosts, const srt_rx_meta *d_meta, uint64_t n,
+                                   uint32_t *d_sockets, srt_err *err);
+
 /* The table as the next run sees it (all may be NULL): associations, slots,
  * the longest probe sequence of a stored key (1: every key in its home slot)
  * and whether a chain runs past the table's end. */
@@ -724,10 +735,11 @@ void srt_deliver_destroy(srt_deliver *dl);
  * The stage is exact, state included, and a pure function of each host's
  * arrival list (ready_ns, socket, priority, size, local flag), the qdisc and
  * bandwidth_up.
- * OUT OF SCOPE: how sockets produce packets (TCP/UDP buffers, retransmission),
- * the loopback relay and the CPU-delay model that reschedules events.  A local
- * packet pushed back into the interface is received as srt_deliver_run
- * receives a forwarded one: srt_deliver_lookup resolves its socket.
+ * OUT OF SCOPE: how sockets produce packets (TCP/UDP buffers, retransmission)
+ * and the CPU-delay model that reschedules events.  The loopback interface is
+ * srt_loopback below.  A local packet pushed back into the interface is
+ * received as srt_deliver_run receives a forwarded one: srt_deliver_lookup, or
+ * srt_deliver_lookup_flat on the device, resolves its socket.
  * ABI: additive to version 4; detect the stage by its symbols. */
 typedef struct srt_outbound srt_outbound;
 
@@ -935,8 +947,9 @@ void srt_sendbatch_destroy(srt_sendbatch *sb);
  * window at a heartbeat time and calls srt_tracker_heartbeat between windows.
  * The reference orders a heartbeat task and a packet event of the same instant
  * by event id, which the library does not own.
- * OUT OF SCOPE: the loopback interface (the tracker's local counters), the
- * tracker's CPU, memory and socket-buffer lines, pcap capture.
+ * The LOCAL counters are the loopback interface's: srt_loopback below.
+ * OUT OF SCOPE: the tracker's CPU, memory and socket-buffer lines, pcap
+ * capture.
  * ABI: additive to version 4; detect the stage by its symbols. */
 typedef struct srt_tracker srt_tracker;
 
@@ -1079,6 +1092,135 @@ srt_status srt_tracker_status(srt_tracker *trk, uint32_t *flags, uint64_t *n_tx_
  * whole string has (as snprintf does), or -1 on a NULL argument. */
 int srt_tracker_counter_string(const srt_trk_counters *c, char *buf, size_t cap);
 void srt_tracker_destroy(srt_tracker *trk);
+
+/* ------------------------------------------------------ loopback interface */
+/* What a host does with the packets its sockets send to 127.0.0.1: the
+ * loopback interface's qdisc, relay_loopback, the receive and the tracker's
+ * LOCAL counters, batched over hosts.  At one host, at one instant t:
+ *   1. every socket-has-data event puts the socket into the loopback
+ *      interface's qdisc unless it is there already (host/host.rs:988-1002,
+ *      network_interface.c:344-370) and notifies the relay; an Idle relay
+ *      schedules ONE forward task at t (relay/mod.rs:110-135: one host event
+ *      id);
+ *   2. the event-order contract of srt_outbound holds: at equal times every
+ *      arrival, in the caller's list order, runs before the forward task.
+ *      relay_loopback is RateLimit::Unlimited (host.rs:307-310) and every
+ *      packet is local, so the task holds no bucket and caches no packet: it
+ *      pops until the interface is empty (relay/mod.rs:200-272), in the
+ *      qdisc's order (SRT_QDISC_FIFO / SRT_QDISC_RR as described above);
+ *   3. each popped packet gets SND_INTERFACE_SENT and is counted by
+ *      tracker_addOutputBytes in the LOCAL out-counters (its source is
+ *      127.0.0.1), gets RELAY_FORWARDED and is pushed into the same interface
+ *      with receive time t;
+ *   4. the push (network_interface.c:140-202) adds RCV_INTERFACE_RECEIVED,
+ *      looks up the specific then the wildcard key in the loopback
+ *      interface's OWN association table, counts the packet in the LOCAL
+ *      in-counters if a socket takes it, else adds RCV_INTERFACE_DROPPED.
+ * So the interface is empty between instants and the stage carries no packet
+ * from call to call: per host only the last instant seen and the number of
+ * forward tasks, and the counters.
+ * LIMIT: in the reference a delivery inside the task can make a socket produce
+ * packets at the same instant (an ACK); the relay is Forwarding, so they join
+ * the running task.  The library owns no sockets: the caller feeds such
+ * packets in a FOLLOWING call with the same ready_ns.  They pop after
+ * everything the earlier call held and take no further event id, which is
+ * exact when the earlier packets had all been popped before the reply was
+ * produced; otherwise the caller must split the instant.  A ready_ns of
+ * UINT64_MAX is not an instant.  Equal priorities within a host's instant are
+ * a caller error under FIFO (their order is then unspecified).
+ * The heartbeat line: the reference prints
+ * inbound-localhost-counters;outbound-localhost-counters;
+ * inbound-remote-counters;outbound-remote-counters (tracker.c:453-519); the
+ * first two are this stage's records, the last two srt_tracker's.
+ * ABI: additive to version 4; detect the stage by its symbols. */
+typedef struct srt_loopback srt_loopback;
+
+#define SRT_LOOPBACK_TIME_ORDER 1u /* a ready_ns below its host's previous arrival: the host's span is not run */
+#define SRT_LOOPBACK_BAD_SOCKET 2u /* socket >= max_sockets: the host's span is not run */
+#define SRT_LOOPBACK_BAD_SLOT   4u /* a socket slot >= n_slots: that side of the packet is counted at its host only */
+
+/* An instance for n_hosts hosts and n_slots socket slots on the plan's device
+ * and stream, or, with plan == NULL, host-only: every array argument named d_
+ * is then a HOST pointer and the calls complete before they return.  Both
+ * forms run the same step and agree bit for bit.  qdisc: SRT_QDISC_*, one for
+ * all hosts; max_sockets (> 0): sockets a host may name; the slots are
+ * srt_tracker's (n_slots == 0 switches the slot counters off).
+ * Memory of the instance, in bytes:
+ *   32 + n_hosts * 184 + n_slots * 160
+ * (the state words; per host the local in and out records, the last instant,
+ * the task count and two packet counts of the last run; per slot the in and
+ * out records), on the device, plus the records and the hosts' words once more
+ * on the host, plus 16 bytes a packet of the largest batch seen: the sort key,
+ * the begin of the packet's instant and the instant's end.  That scratch is the
+ * one thing a call may allocate, when its batch is larger than any before (it
+ * then waits for the stream once).  n_hosts and n_slots are below 2^31.
+ * Destroy the instance before its plan. */
+srt_status srt_loopback_create(srt_plan *plan, uint32_t n_hosts, uint32_t qdisc, uint32_t max_sockets,
+                               uint32_t n_slots, srt_loopback **out, srt_err *err);
+
+/* One call: the packets the hosts' sockets hand to the loopback interface.
+ * dl: an srt_deliver instance of the same plan and n_hosts (else
+ * SRT_ERR_INVALID) that holds the LOOPBACK interface's associations, kept with
+ * srt_deliver_associate / _disassociate; the run uploads the table on the
+ * stream when it has changed since the last upload, as srt_deliver_run does.
+ * d_pkts: n_pkts (< 2^31) srt_out_pkt records grouped by host through
+ * d_host_ptr (n_hosts + 1 entries), each host's in arrival order with
+ * nondecreasing ready_ns; flags and total_size are ignored (every packet is
+ * local).  d_rx_meta[i] and d_trk_meta[i] belong to batch packet i; d_trk_meta
+ * may be NULL: nothing is counted then.  The walk is bounded on the device by
+ * min(d_host_ptr[n_hosts], n_pkts): no host round trip precedes the call.
+ * Outputs, n_pkts entries each, grouped by the INPUT's d_host_ptr (every packet
+ * of an unflagged host is received); position k of host h's span, in the order
+ * the interface receives: d_out_index[k] the packet's batch index,
+ * d_out_socket[k] the socket or UINT32_MAX, d_out_recv_ns[k] the instant
+ * (nondecreasing along the span), d_out_user[k] its rx_meta.user,
+ * d_out_status[k] SND_INTERFACE_SENT | RELAY_FORWARDED | RCV_INTERFACE_RECEIVED,
+ * plus RCV_INTERFACE_DROPPED when no socket took it.
+ * Counters: every popped packet is counted on the out side at its host and at
+ * d_trk_meta[i].socket_slot; on the in side iff a socket took it, at its host
+ * and at the slot the returned socket names (srt_tracker_rx's convention), in
+ * srt_tracker's classes.  A slot >= n_slots (n_slots > 0) raises BAD_SLOT and
+ * that side of the packet is counted at its host only.
+ * Tasks: one per host for each distinct instant; an arrival whose ready_ns
+ * equals the host's last instant of an EARLIER call starts no new task (the
+ * LIMIT above).
+ * A host with a ready_ns below its previous arrival, in this call or an
+ * earlier one (TIME_ORDER), or with a socket >= max_sockets (BAD_SOCKET) is
+ * flagged: its state and counters stay untouched and its whole span is written
+ * in identity order with status 0, socket UINT32_MAX, recv_ns UINT64_MAX and
+ * the user copied.  The other hosts' results stay exact.  Every write is
+ * range-checked first: a flagged call never reads or writes out of bounds.
+ * An instant of any length is ordered in the same call, in time quadratic in
+ * its length shared by the 8 or 64 lanes that own its host.
+ * Asynchronous on the plan's stream: it reads nothing back. */
+srt_status srt_loopback_run(srt_loopback *lb, srt_deliver *dl, const srt_out_pkt *d_pkts, const uint32_t *d_host_ptr,
+                            uint64_t n_pkts, const srt_rx_meta *d_rx_meta, const srt_trk_meta *d_trk_meta,
+                            uint32_t *d_out_index, uint32_t *d_out_socket, uint64_t *d_out_recv_ns,
+                            uint32_t *d_out_user, uint32_t *d_out_status, srt_err *err);
+
+/* srt_tracker_heartbeat for the local records, with its semantics throughout:
+ * synchronises, returns the selected records and clears exactly those; a NULL
+ * selection means all; an index out of range returns SRT_ERR_INVALID and clears
+ * nothing; an index named twice is returned twice and cleared once.
+ * srt_tracker_counter_string formats a record. */
+srt_status srt_loopback_heartbeat(srt_loopback *lb, const uint32_t *hosts, uint32_t n_sel_hosts,
+                                  const uint32_t *slots, uint32_t n_sel_slots, srt_trk_counters *out_node_in,
+                                  srt_trk_counters *out_node_out, srt_trk_counters *out_slot_in,
+                                  srt_trk_counters *out_slot_out, srt_err *err);
+
+/* Synchronises; out_tasks[h] (n_hosts entries, HOST pointer): the forward tasks
+ * host h's loopback relay has scheduled since create, each one host event id. */
+srt_status srt_loopback_tasks(srt_loopback *lb, uint64_t *out_tasks, srt_err *err);
+
+/* Synchronises the stream.  *flags (may be NULL): the SRT_LOOPBACK_* conditions
+ * met since the last status call (then cleared); *n_received / *n_no_socket
+ * (may be NULL): the last run's received packets and those of them no socket
+ * took (the device form sums the hosts' counts here, with one launch).
+ * SRT_ERR_INVALID, with a message that names every flag set, when any was;
+ * else SRT_OK. */
+srt_status srt_loopback_status(srt_loopback *lb, uint32_t *flags, uint64_t *n_received, uint64_t *n_no_socket,
+                               srt_err *err);
+void srt_loopback_destroy(srt_loopback *lb);
 
 /* ---------------------------------------------------- IP assignment (a10) */
 /* IpAssignment<u32> (src/main/network/graph/mod.rs:352-420): IPv4 address ->

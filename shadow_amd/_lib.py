@@ -46,6 +46,8 @@ DELIVER_OUT_OVERFLOW, DELIVER_LOG_OVERRUN, DELIVER_NOTE_OVERRUN, DELIVER_BAD_HOS
 # srt_trk_meta flags, srt_tracker_status flags
 TRK_RETRANS = 1
 TRACKER_LOG_OVERRUN, TRACKER_NOTE_OVERRUN, TRACKER_BAD_SOCKET, TRACKER_BAD_HOST = 1, 2, 4, 8
+# srt_loopback_status flags
+LOOPBACK_TIME_ORDER, LOOPBACK_BAD_SOCKET, LOOPBACK_BAD_SLOT = 1, 2, 4
 
 
 class SrtErr(C.Structure):
@@ -192,6 +194,7 @@ SIGNATURES = {
     "srt_deliver_associate": (C.c_int, [_vp, _vp, C.c_uint64, _errp]),
     "srt_deliver_disassociate": (C.c_int, [_vp, _vp, C.c_uint64, _errp]),
     "srt_deliver_lookup": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _errp]),
+    "srt_deliver_lookup_flat": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _errp]),
     "srt_deliver_table_stats": (C.c_int, [_vp, _u64p, _u32p, _u32p, _u32p, _errp]),
     "srt_deliver_note": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _errp]),
     "srt_deliver_run": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp,
@@ -207,6 +210,12 @@ SIGNATURES = {
     "srt_tracker_status": (C.c_int, [_vp, _u32p, _u64p, _u64p, _errp]),
     "srt_tracker_counter_string": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "srt_tracker_destroy": (None, [_vp]),
+    "srt_loopback_create": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp), _errp]),
+    "srt_loopback_run": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _errp]),
+    "srt_loopback_heartbeat": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _errp]),
+    "srt_loopback_tasks": (C.c_int, [_vp, _u64p, _errp]),
+    "srt_loopback_status": (C.c_int, [_vp, _u32p, _u64p, _u64p, _errp]),
+    "srt_loopback_destroy": (None, [_vp]),
     "srt_routing_info_build": (C.c_int, [C.POINTER(SrtCsr), _u32p, C.c_uint32, C.c_int, C.POINTER(SrtOpts),
                                          C.POINTER(_vp), _errp]),
     "srt_routing_info_from_plan": (C.c_int, [_vp, C.POINTER(_vp), _errp]),

@@ -39,6 +39,11 @@
 // words with one more launch.  (One atomic a wave on a call-wide counter
 // measured 144 us for the scatter of 1M packets and 136 us for the late order
 // of 500k: 10k dependent atomics on one address.)
+// Lookup alone (srt_deliver_lookup_flat), one launch: one thread a (host, meta)
+// record over the same probe, for the SRT_OUT_LOCAL packets of an outbound
+// call, which never reach the inbound stage.  The loopback interface's stage
+// (srt_loopback.hip) takes an instance's table through srt::deliver_table,
+// the upload path of the run.
 // Every value is written with ordinary stores from plain C++.
 #include <algorithm>
 #include <cstdio>
@@ -215,6 +220,17 @@ __global__ __launch_bounds__(ST) void deliver_sum_kernel(const deliver::Ctx c) {
     }
 }
 
+// srt_deliver_lookup_flat: one thread a record over the stage's own lookup
+__global__ __launch_bounds__(BT) void deliver_lookup_kernel(const deliver::Slot *__restrict__ table, uint32_t mask,
+                                                            uint32_t n_hosts, const uint32_t *__restrict__ hosts,
+                                                            const srt_rx_meta *__restrict__ meta, uint32_t n,
+                                                            uint32_t *__restrict__ sockets) {
+    const uint64_t k = (uint64_t)blockIdx.x * BT + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t h = hosts[k];
+    sockets[k] = h < n_hosts ? deliver::lookup(table, mask, h, meta[k]) : deliver::NO_SOCKET;
+}
+
 void set_err(srt_err *err, srt_status code, const char *msg) {
     if (!err) return;
     err->code = code;
@@ -310,6 +326,19 @@ namespace srt {
 hipError_t preload_deliver() {
     hipFuncAttributes a;
     return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&deliver_scan_kernel));
+}
+
+// the table for a launch of another stage on the same stream (srt_loopback_run)
+srt_status deliver_table(srt_deliver *dl, srt_plan **plan, uint32_t *n_hosts, const deliver::Slot **table,
+                         uint32_t *mask, srt_err *err) {
+    *plan = dl->plan;
+    *n_hosts = dl->n_hosts;
+    if (dl->plan && hipSetDevice(dl->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    const srt_status up = upload(dl, err);
+    if (up != SRT_OK) return up;
+    *table = dl->plan ? dl->d_table : dl->h_table.data();
+    *mask = dl->slots - 1;
+    return SRT_OK;
 }
 }  // namespace srt
 
@@ -449,6 +478,30 @@ extern "C" srt_status srt_deliver_lookup(srt_deliver *dl, const uint32_t *hosts,
         return SRT_ERR_OOM;
     }
     for (uint64_t k = 0; k < n; ++k) sockets[k] = deliver::lookup(dl->h_table.data(), dl->slots - 1, hosts[k], meta[k]);
+    return SRT_OK;
+}
+
+extern "C" srt_status srt_deliver_lookup_flat(srt_deliver *dl, const uint32_t *d_hosts, const srt_rx_meta *d_meta,
+                                              uint64_t n, uint32_t *d_sockets, srt_err *err) {
+    if (!dl || !dl->plan) return srt_deliver_lookup(dl, d_hosts, d_meta, n, d_sockets, err);
+    if (err) std::memset(err, 0, sizeof *err);
+    if (n && (!d_hosts || !d_meta || !d_sockets)) {
+        set_err(err, SRT_ERR_INVALID, "null argument");
+        return SRT_ERR_INVALID;
+    }
+    if (n >= 0x80000000ull) {
+        set_err(err, SRT_ERR_INVALID, "more than 2^31-1 records in one call");
+        return SRT_ERR_INVALID;
+    }
+    if (hipSetDevice(dl->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    const srt_status up = upload(dl, err);
+    if (up != SRT_OK || !n) return up;
+    hipLaunchKernelGGL(deliver_lookup_kernel, dim3((uint32_t)((n + BT - 1) / BT)), dim3(BT), 0, dl->plan->stream,
+                       dl->d_table, dl->slots - 1, dl->n_hosts, d_hosts, d_meta, (uint32_t)n, d_sockets);
+    if (hipGetLastError() != hipSuccess) {
+        set_err(err, SRT_ERR_HIP, "deliver: launch failed");
+        return SRT_ERR_HIP;
+    }
     return SRT_OK;
 }
 

@@ -3093,6 +3093,7 @@ hipError_t preload_sendbatch();
 hipError_t preload_flight();
 hipError_t preload_deliver();
 hipError_t preload_tracker();
+hipError_t preload_loopback();
 hipError_t preload_kernels() {
     hipError_t e = preload_fw();
     if (e == hipSuccess) e = preload_loss();
@@ -3107,6 +3108,7 @@ hipError_t preload_kernels() {
     if (e == hipSuccess) e = preload_flight();
     if (e == hipSuccess) e = preload_deliver();
     if (e == hipSuccess) e = preload_tracker();
+    if (e == hipSuccess) e = preload_loopback();
     return e;
 }
 

@@ -413,6 +413,10 @@ struct srt_plan {
     unsigned long long *h_tinfo = nullptr; // pinned copy of d_tinfo
 };
 
+namespace deliver {
+struct Slot;  // srt_deliver_step.h: one association of the flat table
+}
+
 namespace srt {
 // plan creation's kernels, timed by event pairs on the plan's stream while
 // p->in_create (srt_timing.create_device_ms sums them; host work between the
@@ -469,6 +473,19 @@ srt_status routing_build(const srt_csr *g, const uint32_t *nodes, uint32_t n, co
 void init_wait();
 // loads the code object of every kernel translation unit (srt_init)
 hipError_t preload_kernels();
+// srt_deliver.hip: the instance's association table as the next launch on its plan's stream sees it
+// (rebuilt on the host and uploaded on the stream when the associations have changed since the last
+// upload: srt_deliver_run's own path), with the instance's plan (nullptr: host-only) and n_hosts
+srt_status deliver_table(srt_deliver *dl, srt_plan **plan, uint32_t *n_hosts, const deliver::Slot **table,
+                         uint32_t *mask, srt_err *err);
+// srt_tracker.hip: tracker_heartbeat over four contiguous srt_trk_counters arrays at `recs` (hosts in,
+// hosts out, slots in, slots out): synchronises, returns the selected records and clears exactly those;
+// `stage` takes the copy on the host when `recs` is device memory (plan != nullptr)
+srt_status counters_heartbeat(srt_plan *plan, const char *who, srt_trk_counters *recs, size_t rec_bytes,
+                              srt_trk_counters *stage, uint32_t n_hosts, uint32_t n_sockets, const uint32_t *hosts,
+                              uint32_t n_sel_hosts, const uint32_t *sockets, uint32_t n_sel_sockets,
+                              srt_trk_counters *out_node_in, srt_trk_counters *out_node_out,
+                              srt_trk_counters *out_sock_in, srt_trk_counters *out_sock_out, srt_err *err);
 // collectives (srt_comm.cpp)
 srt_status comm_bcast(srt_comm *c, void *buf, size_t bytes, int root, hipStream_t s, srt_err *err);
 srt_status comm_allgather_inplace(srt_comm *c, void *buf, size_t bytes_per_rank, hipStream_t s,

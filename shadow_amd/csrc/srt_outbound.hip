@@ -13,8 +13,10 @@
 // bucket, relay loop, event order, carry-over -- is srt_outbound_step.h,
 // compiled here for the device and for the host-only instance alike.
 //
-// Out of scope: how sockets produce packets, the loopback relay, the CPU-delay
-// model, and what the interface does with a local packet pushed back into it.
+// Out of scope: how sockets produce packets and the CPU-delay model.  The
+// loopback relay is srt_loopback.hip; a local packet pushed back into this
+// interface is resolved with srt_deliver_lookup_flat (srt_deliver.hip), its
+// order among the call's local packets staying the caller's.
 //
 // Device form, two launches a call on the plan's stream:
 //   (1) preset: one thread a batch packet: status 0, send_ns and send_rank

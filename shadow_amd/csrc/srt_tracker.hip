@@ -396,44 +396,45 @@ extern "C" srt_status srt_tracker_rx_flat(srt_tracker *trk, const uint32_t *d_ho
     return launched(err);
 }
 
-extern "C" srt_status srt_tracker_heartbeat(srt_tracker *trk, const uint32_t *hosts, uint32_t n_sel_hosts,
-                                            const uint32_t *sockets, uint32_t n_sel_sockets,
-                                            srt_trk_counters *out_node_in, srt_trk_counters *out_node_out,
-                                            srt_trk_counters *out_sock_in, srt_trk_counters *out_sock_out,
-                                            srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!trk) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
-    const uint32_t nh = hosts ? n_sel_hosts : trk->n_hosts, ns = sockets ? n_sel_sockets : trk->n_sockets;
+namespace srt {
+// tracker_heartbeat over the four contiguous record arrays at `recs` (hosts in, hosts out, slots in,
+// slots out; device memory with a plan, whose `stage` then takes the copy on the host)
+srt_status counters_heartbeat(srt_plan *plan, const char *who, srt_trk_counters *recs, size_t rec_bytes,
+                              srt_trk_counters *stage, uint32_t n_hosts, uint32_t n_sockets, const uint32_t *hosts,
+                              uint32_t n_sel_hosts, const uint32_t *sockets, uint32_t n_sel_sockets,
+                              srt_trk_counters *out_node_in, srt_trk_counters *out_node_out,
+                              srt_trk_counters *out_sock_in, srt_trk_counters *out_sock_out, srt_err *err) {
+    char msg[160];
+    const uint32_t nh = hosts ? n_sel_hosts : n_hosts, ns = sockets ? n_sel_sockets : n_sockets;
     for (uint32_t k = 0; hosts && k < nh; ++k)
-        if (hosts[k] >= trk->n_hosts) {
-            set_err(err, SRT_ERR_INVALID, "tracker: a selected host is not below n_hosts (nothing was cleared)");
+        if (hosts[k] >= n_hosts) {
+            std::snprintf(msg, sizeof msg, "%s: a selected host is not below n_hosts (nothing was cleared)", who);
+            set_err(err, SRT_ERR_INVALID, msg);
             return SRT_ERR_INVALID;
         }
     for (uint32_t k = 0; sockets && k < ns; ++k)
-        if (sockets[k] >= trk->n_sockets) {
-            set_err(err, SRT_ERR_INVALID, "tracker: a selected socket slot is not below n_sockets (nothing was cleared)");
+        if (sockets[k] >= n_sockets) {
+            std::snprintf(msg, sizeof msg, "%s: a selected socket slot is not below n_sockets (nothing was cleared)", who);
+            set_err(err, SRT_ERR_INVALID, msg);
             return SRT_ERR_INVALID;
         }
     // the four record arrays as the host sees them: the instance's own memory, or the staged copy
-    srt_trk_counters *recs = trk->base.node_in;
+    srt_trk_counters *dev = recs;
     const bool all = !hosts && !sockets;
-    if (trk->plan) {
-        if (hipSetDevice(trk->plan->device) != hipSuccess) return SRT_ERR_HIP;
-        hipStream_t s = trk->plan->stream;
-        recs = trk->stage.data();
-        if ((trk->rec_bytes &&
-             hipMemcpyAsync(recs, trk->base.node_in, trk->rec_bytes, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+    if (plan) {
+        if (hipSetDevice(plan->device) != hipSuccess) return SRT_ERR_HIP;
+        hipStream_t s = plan->stream;
+        recs = stage;
+        if ((rec_bytes && hipMemcpyAsync(recs, dev, rec_bytes, hipMemcpyDeviceToHost, s) != hipSuccess) ||
             hipStreamSynchronize(s) != hipSuccess) {
             (void)hipGetLastError();
-            set_err(err, SRT_ERR_HIP, "tracker: stream failed");
+            std::snprintf(msg, sizeof msg, "%s: stream failed", who);
+            set_err(err, SRT_ERR_HIP, msg);
             return SRT_ERR_HIP;
         }
     }
-    srt_trk_counters *node_in = recs, *node_out = node_in + trk->n_hosts, *sock_in = node_out + trk->n_hosts,
-                     *sock_out = sock_in + trk->n_sockets;
+    srt_trk_counters *node_in = recs, *node_out = node_in + n_hosts, *sock_in = node_out + n_hosts,
+                     *sock_out = sock_in + n_sockets;
     for (uint32_t k = 0; k < nh; ++k) {
         const uint32_t h = hosts ? hosts[k] : k;
         if (out_node_in) out_node_in[k] = node_in[h];
@@ -448,18 +449,35 @@ extern "C" srt_status srt_tracker_heartbeat(srt_tracker *trk, const uint32_t *ho
     const srt_trk_counters zero = {};
     for (uint32_t k = 0; k < nh; ++k) node_in[hosts ? hosts[k] : k] = node_out[hosts ? hosts[k] : k] = zero;
     for (uint32_t k = 0; k < ns; ++k) sock_in[sockets ? sockets[k] : k] = sock_out[sockets ? sockets[k] : k] = zero;
-    if (trk->plan && trk->rec_bytes && (nh || ns)) {
+    if (plan && rec_bytes && (nh || ns)) {
         // the stream is idle: the cleared copy goes back whole (everything selected: a memset)
-        hipStream_t s = trk->plan->stream;
-        const hipError_t e = all ? hipMemsetAsync(trk->base.node_in, 0, trk->rec_bytes, s)
-                                 : hipMemcpyAsync(trk->base.node_in, recs, trk->rec_bytes, hipMemcpyHostToDevice, s);
+        hipStream_t s = plan->stream;
+        const hipError_t e = all ? hipMemsetAsync(dev, 0, rec_bytes, s)
+                                 : hipMemcpyAsync(dev, recs, rec_bytes, hipMemcpyHostToDevice, s);
         if (e != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
             (void)hipGetLastError();
-            set_err(err, SRT_ERR_HIP, "tracker: clearing the records failed");
+            std::snprintf(msg, sizeof msg, "%s: clearing the records failed", who);
+            set_err(err, SRT_ERR_HIP, msg);
             return SRT_ERR_HIP;
         }
     }
     return SRT_OK;
+}
+}  // namespace srt
+
+extern "C" srt_status srt_tracker_heartbeat(srt_tracker *trk, const uint32_t *hosts, uint32_t n_sel_hosts,
+                                            const uint32_t *sockets, uint32_t n_sel_sockets,
+                                            srt_trk_counters *out_node_in, srt_trk_counters *out_node_out,
+                                            srt_trk_counters *out_sock_in, srt_trk_counters *out_sock_out,
+                                            srt_err *err) {
+    if (err) std::memset(err, 0, sizeof *err);
+    if (!trk) {
+        set_err(err, SRT_ERR_INVALID, "null argument");
+        return SRT_ERR_INVALID;
+    }
+    return srt::counters_heartbeat(trk->plan, "tracker", trk->base.node_in, trk->rec_bytes, trk->stage.data(),
+                                   trk->n_hosts, trk->n_sockets, hosts, n_sel_hosts, sockets, n_sel_sockets,
+                                   out_node_in, out_node_out, out_sock_in, out_sock_out, err);
 }
 
 extern "C" srt_status srt_tracker_status(srt_tracker *trk, uint32_t *flags, uint64_t *n_tx_counted,

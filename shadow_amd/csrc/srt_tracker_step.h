@@ -8,7 +8,9 @@
 // payload > 0 is data, else control, SRT_TRK_RETRANS (PDS_SND_TCP_RETRANSMITTED)
 // selects the retransmit class.  Kept per host and per socket slot, in and out,
 // REMOTE only: on the internet interface no packet has the loopback address, an
-// SRT_OUT_LOCAL packet included.  The loopback interface is out of scope.
+// SRT_OUT_LOCAL packet included.  The LOCAL counters are the loopback
+// interface's: srt_loopback_step.h, which uses the classes and record helpers
+// below.
 //
 // Output side (networkinterface_pop, network_interface.c:310-340): a packet is
 // counted in the call in which the interface popped it, forwarded or not:

@@ -703,8 +703,23 @@ class DeliverStage:
                                                  C.byref(err)), err)
         return out
 
+    def lookup_flat(self, hosts, meta, sockets):
+        """srt_deliver_lookup_flat: hosts int32/uint32 [n], meta a uint8 view of
+        n 16-byte srt_rx_meta records, the output sockets int32/uint32 [n]
+        (0xffffffff: none, a host >= n_hosts included).  Device form: enqueue
+        only; the table is uploaded first when it has changed."""
+        n = self._nbytes(hosts) // 4
+        if self._nbytes(meta) < 16 * n or self._nbytes(sockets) < 4 * n:
+            raise ValueError("DeliverStage.lookup_flat: an array is smaller than its record count")
+        cur, ps = self._streams(hosts) if n else (None, None)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_deliver_lookup_flat(self._h, self._ptr(hosts), self._ptr(meta), n,
+                                                      self._ptr(sockets), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)
+
     def table_stats(self):
-        """srt_deliver_table_stats -> (associations, slots, longest probe sequence, a chain wraps the end)"""
+        """srt_deliver_table_stats ->(associations, slots, longest probe sequence, a chain wraps the end)"""
         n, s, p, w, err = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint32(), _lib.SrtErr()
         _lib.check(_lib.lib().srt_deliver_table_stats(self._h, C.byref(n), C.byref(s), C.byref(p), C.byref(w),
                                                       C.byref(err)), err)
@@ -917,6 +932,114 @@ class Tracker:
     def close(self):
         if self._h:
             _lib.lib().srt_tracker_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LoopbackRelay:
+    """srt_loopback: the loopback interface of every host -- the qdisc's order
+    at each instant, relay_loopback's forward task, the receive with the
+    loopback interface's own associations (a DeliverStage of the same plan and
+    n_hosts) and the tracker's local counters, one fused call.  run() orders,
+    looks up and counts; heartbeat() returns and clears the selected local
+    records (TRK_COUNTERS_DTYPE, Tracker.counter_string formats them); tasks()
+    gives the forward tasks scheduled a host.
+
+    Bound to a RoutingPlan (arrays are torch CUDA tensors of its device, the
+    calls are asynchronous on its stream; closing the plan closes it), or
+    host-only with plan=None (arrays are numpy arrays, the same step on the
+    CPU)."""
+
+    def __init__(self, plan: Optional[RoutingPlan], n_hosts: int, qdisc: int, max_sockets: int, n_slots: int):
+        self.plan = plan
+        self.n_hosts, self.n_slots = int(n_hosts), int(n_slots)
+        self._h = C.c_void_p()
+        if plan is not None:
+            _bind_to_plan(self, plan)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_loopback_create(plan.handle if plan is not None else None, self.n_hosts, int(qdisc),
+                                                  int(max_sockets), self.n_slots, C.byref(self._h), C.byref(err)), err)
+
+    _ptr = staticmethod(InboundRouter._ptr)
+    _nbytes = staticmethod(SendBatch._nbytes)
+    _streams = FlightStore._streams
+
+    def run(self, deliver: DeliverStage, pkts, host_ptr, rx_meta, trk_meta, out_index, out_socket, out_recv_ns,
+            out_user, out_status):
+        """srt_loopback_run.  deliver: the DeliverStage that holds the loopback
+        interface's associations; pkts a uint8 view of 32-byte srt_out_pkt
+        records (OUT_PKT_DTYPE) grouped by host, host_ptr int32/uint32
+        [n_hosts+1], rx_meta and trk_meta uint8 views of 16-byte records, one
+        a packet (trk_meta None: nothing is counted).  Outputs [n_pkts]:
+        out_index, out_socket, out_user, out_status int32/uint32, out_recv_ns
+        int64/uint64.  Device form: enqueue only."""
+        n_pkts = self._nbytes(pkts) // 32
+        if self._nbytes(host_ptr) < 4 * (self.n_hosts + 1) or self._nbytes(rx_meta) < 16 * n_pkts or \
+                (trk_meta is not None and self._nbytes(trk_meta) < 16 * n_pkts) or \
+                self._nbytes(out_index) < 4 * n_pkts or self._nbytes(out_socket) < 4 * n_pkts or \
+                self._nbytes(out_recv_ns) < 8 * n_pkts or self._nbytes(out_user) < 4 * n_pkts or \
+                self._nbytes(out_status) < 4 * n_pkts:
+            raise ValueError("LoopbackRelay.run: an array is smaller than its record count")
+        cur, ps = self._streams(host_ptr)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_loopback_run(
+            self._h, deliver._h, self._ptr(pkts), self._ptr(host_ptr), n_pkts, self._ptr(rx_meta),
+            self._ptr(trk_meta), self._ptr(out_index), self._ptr(out_socket), self._ptr(out_recv_ns),
+            self._ptr(out_user), self._ptr(out_status), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)
+
+    def heartbeat(self, hosts=None, slots=None):
+        """srt_loopback_heartbeat: synchronises; returns (node_in, node_out,
+        slot_in, slot_out), TRK_COUNTERS_DTYPE record arrays of the local
+        counters for the selected hosts and socket slots (None: all; an empty
+        list: none), and clears exactly those records."""
+        def sel(x, n_all):
+            if x is None:
+                return None, n_all
+            a = np.ascontiguousarray(x, np.uint32).reshape(-1)
+            if not len(a):
+                return np.zeros(1, np.uint32), 0  # a selection of none: a non-NULL pointer, count 0
+            return a, len(a)
+
+        hs, nh = sel(hosts, self.n_hosts)
+        ss, ns = sel(slots, self.n_slots)
+        outs = [np.zeros(nh, TRK_COUNTERS_DTYPE), np.zeros(nh, TRK_COUNTERS_DTYPE),
+                np.zeros(ns, TRK_COUNTERS_DTYPE), np.zeros(ns, TRK_COUNTERS_DTYPE)]
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_loopback_heartbeat(
+            self._h, None if hs is None else hs.ctypes.data, nh, None if ss is None else ss.ctypes.data, ns,
+            *[o.ctypes.data if len(o) else None for o in outs], C.byref(err)), err)
+        return tuple(outs)
+
+    def tasks(self) -> np.ndarray:
+        """srt_loopback_tasks: synchronises; the forward tasks every host's
+        loopback relay has scheduled since create (uint64 [n_hosts])."""
+        out = np.zeros(self.n_hosts, np.uint64)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_loopback_tasks(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(err)),
+                   err)
+        return out
+
+    def status(self, check: bool = True):
+        """srt_loopback_status: synchronises; (flags, the last run's received
+        packets, those no socket took).  check=True raises SrtError when a
+        flag is set."""
+        flags, a, b = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        err = _lib.SrtErr()
+        rc = _lib.lib().srt_loopback_status(self._h, C.byref(flags), C.byref(a), C.byref(b), C.byref(err))
+        if check or (rc != _lib.SRT_OK and not flags.value):
+            _lib.check(rc, err)
+        return flags.value, a.value, b.value
+
+    def close(self):
+        if self._h:
+            _lib.lib().srt_loopback_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
