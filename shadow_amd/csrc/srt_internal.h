@@ -50,9 +50,10 @@ constexpr uint32_t LEVEL_V_MAX = 18400;
 // ... its stages that spare full-row passes around a level's walk (knob
 // SRT_LVL_LEAN; level_solve_kernel's `lean`): small push levels of the packed
 // row list their members instead of a scan of the row, and its `idn` output
-// pass leaves the row initialised for the workgroup's next one
-constexpr uint32_t LVL_LEAN_LIST = 2, LVL_LEAN_INIT = 4;
-constexpr uint32_t LVL_LEAN_ALL = LVL_LEAN_LIST | LVL_LEAN_INIT;
+// pass leaves the row initialised for the workgroup's next one; the other
+// push-only levels are walked one wave an item (SRT_LVL_LEAN=6: without)
+constexpr uint32_t LVL_LEAN_LIST = 2, LVL_LEAN_INIT = 4, LVL_LEAN_WAVE = 8;
+constexpr uint32_t LVL_LEAN_ALL = LVL_LEAN_LIST | LVL_LEAN_INIT | LVL_LEAN_WAVE;
 constexpr uint32_t LVL_LEAN_KEPT = LVL_LEAN_ALL;
 
 // In-edge of the sparse SSSP (srt_sssp.hip): the source vertex u of an

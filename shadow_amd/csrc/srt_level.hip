@@ -425,6 +425,23 @@ __constant__ uint32_t lvl_diag;                // level solve ablations (SRT_LVL
 constexpr uint32_t LIST_T = SRT_LIST_T;
 constexpr uint32_t LIST_LPI = PACK_NT / LIST_T;  // lanes an item of a listed level
 static_assert(LIST_T >= 1 && LIST_T * LIST_LPI == PACK_NT, "a listed level's items share the workgroup evenly");
+// The wave walk of the other push-only levels of the packed row (LVL_LEAN_WAVE):
+// WAVE_B: items of a batch, dealt to the waves by a counter; WAVE_D: 64-entry
+// passes in flight; WAVE_U: passes folded together (C3: 8 / 4 3.49 ms the solve,
+// 4 / 2 3.65, 4 / 1 3.79, 12 / 4 3.78; 32 items a batch +0.14).
+#ifndef SRT_WAVE_B
+#define SRT_WAVE_B 64
+#endif
+#ifndef SRT_WAVE_D
+#define SRT_WAVE_D 8
+#endif
+#ifndef SRT_WAVE_U
+#define SRT_WAVE_U 4
+#endif
+constexpr uint32_t WAVE_B = SRT_WAVE_B;
+constexpr int WAVE_D = SRT_WAVE_D, WAVE_U = SRT_WAVE_U;
+static_assert(WAVE_B >= 1 && WAVE_B <= 64, "a batch's items: a lane each");
+static_assert(WAVE_U >= 1 && WAVE_D % WAVE_U == 0, "the ring is folded in whole groups");
 // probe != nullptr: no table; probe[2 + k] = the largest level over the
 // in-use columns of row k (0xffff if one is unreached by level lcap), the u64
 // at probe[0] += the edges walked.
@@ -700,6 +717,9 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
             // (state 3; every later hit finds state 1) appends it to the members
             bool listed = false;
             if constexpr (PK) listed = T <= list_t && !plan_pull;
+            // ... and one of more items is walked a wave an item (LVL_LEAN_WAVE; uniform)
+            bool waved = false;
+            if constexpr (PK) waved = (lean & LVL_LEAN_WAVE) && T > list_t && !plan_pull;
             if (PK && listed) {
                 const uint32_t t = tid / LIST_LPI, ls = tid % LIST_LPI;
                 if (t < T) {
@@ -713,6 +733,102 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                         const uint32_t b = __float_as_uint(1.0f - __fmul_rn(onem, __uint_as_float((uint32_t)(wd >> 32))));
                         if (key[o] > PACK_LOSS && atomicMin(&key[o], 1u << 30 | (b & PACK_LOSS)) >= 3u << 30)
                             mem[settled + atomicAdd(&cur[par][1], 1u)] = (uint16_t)o;
+                    }
+                }
+            } else if (PK && waved) {
+                // One wave an item: what a lane group of the chunk walk below works out
+                // in vector registers a chunk (which item and chunk come next, the
+                // entry address, the slot bounds) is uniform in the wave here and is
+                // scalar work.  Batches of `bs` items are dealt by the level's counter
+                // (cur[par][0]: a push-only level compacts no unsettled list); lane i of
+                // a batch fetches item t0 + i (its list and 1 - loss of its vertex).
+                // The batch's lists then go by as one stream of passes of 64 entries, a
+                // lane an entry, the mins under one exec mask: lane p works out pass
+                // p's list place, length and 1 - loss once a batch, and a pass costs
+                // three readlanes and no branch.  A pass is loaded WAVE_D passes ahead
+                // of its fold, a ring in registers; every step loads (lanes past the
+                // list its last entry, steps past the last pass that pass again), so
+                // the loads in flight can be counted.  WAVE_U passes are folded
+                // together (their probes, then their mins), so that one's LDS latency
+                // hides behind the others'.  The candidate is the chunk walk's; its min
+                // goes out where the chunk walk's select keeps it.
+                constexpr int D = WAVE_D, U = WAVE_U;
+                const uint32_t Tu = __builtin_amdgcn_readfirstlane(T);
+                const uint32_t per = (Tu + PACK_NT / 64 - 1) / (PACK_NT / 64);
+                const uint32_t bs = per < WAVE_B ? per : WAVE_B;  // a small level: every wave a share
+                for (;;) {
+                    uint32_t bi = 0;
+                    if (lane == 0) bi = atomicAdd(&cur[par][0], 1u);
+                    const uint32_t t0 = (uint32_t)__builtin_amdgcn_readfirstlane(bi) * bs;
+                    if (t0 >= Tu) break;
+                    const uint32_t nb = Tu - t0 < bs ? Tu - t0 : bs;
+                    uint32_t w = 1, x = 0, e0 = 0, e1 = 0;
+                    float onem = 0.0f;
+                    if ((uint32_t)lane < nb) {
+                        item(t0 + lane, w, x, e0, e1);
+                        onem = 1.0f - __uint_as_float(key[x] & PACK_LOSS);
+                    }
+                    const uint32_t len = e1 - e0;  // (lanes past the batch: 0)
+                    vis32 += len;
+                    // the batch's passes in list order: pass p lies in the item whose
+                    // running count of passes is the first above p (a search over the
+                    // lanes' inclusive counts), a window of 64 passes a lane each
+                    const uint32_t np = (len + 63u) >> 6;
+                    uint32_t incl = np;
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const uint32_t y = __shfl_up(incl, o);
+                        if (lane >= o) incl += y;
+                    }
+                    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane(incl, 63);
+                    for (uint32_t win = 0; win < total; win += 64u) {
+                    const uint32_t p = win + lane;
+                    uint32_t it = 0;  // the items whose passes all lie before p (<= 63)
+#pragma unroll
+                    for (uint32_t sb = 32; sb; sb >>= 1)
+                        if ((uint32_t)__shfl(incl, it + sb - 1u) <= p) it += sb;
+                    const uint32_t il = __shfl(len, it);
+                    const uint32_t j = p - ((uint32_t)__shfl(incl, it) - ((il + 63u) >> 6));  // pass j of item `it`
+                    // pass p (a lane past the last: never read): first entry, entries from it on, 1 - loss
+                    const uint32_t pb = (uint32_t)__shfl(e0, it) + 64u * j, pr = il - 64u * j;
+                    const uint32_t pom = __shfl(__float_as_uint(onem), it);
+                    const uint32_t nq = total - win < 64u ? total - win : 64u;
+                    uint2 ring[D];
+                    uint32_t rrem[D], rom[D];  // a ring slot's entries (0: none) and 1 - loss, uniform
+                    auto issue = [&](int r, uint32_t q) {
+                        const uint32_t qc = q < nq ? q : nq - 1u;
+                        const uint32_t rm = (uint32_t)__builtin_amdgcn_readlane(pr, qc);
+                        rrem[r] = q < nq ? rm : 0u;
+                        rom[r] = (uint32_t)__builtin_amdgcn_readlane(pom, qc);
+                        const uint32_t o = (uint32_t)lane < rm - 1u ? (uint32_t)lane : rm - 1u;
+                        ring[r] = reinterpret_cast<const uint2 *>(ce_out + (uint32_t)__builtin_amdgcn_readlane(pb, qc))[o];
+                    };
+#pragma unroll
+                    for (int r = 0; r < D; ++r) issue(r, r);
+                    for (uint32_t q0 = 0; q0 < nq; q0 += D) {
+#pragma unroll
+                        for (int r0 = 0; r0 < D; r0 += U) {
+                            // (every lane holds an entry of the list: the probes and the
+                            // candidates need no mask, the mins alone do)
+#if SRT_PK_PROBE
+                            uint32_t ko[U];
+#pragma unroll
+                            for (int u = 0; u < U; ++u) ko[u] = key[ring[r0 + u].x];
+#endif
+#pragma unroll
+                            for (int u = 0; u < U; ++u) {
+                                const uint2 wd = ring[r0 + u];
+                                const uint32_t b = __float_as_uint(1.0f - __fmul_rn(__uint_as_float(rom[r0 + u]), __uint_as_float(wd.y)));
+#if SRT_PK_PROBE
+                                if ((uint32_t)lane < rrem[r0 + u] && ko[u] > PACK_LOSS)
+#else
+                                if ((uint32_t)lane < rrem[r0 + u])
+#endif
+                                    atomicMin(&key[wd.x], 1u << 30 | (b & PACK_LOSS));
+                            }
+#pragma unroll
+                            for (int u = 0; u < U; ++u) issue(r0 + u, q0 + r0 + u + D);
+                        }
+                    }
                     }
                 }
             } else
