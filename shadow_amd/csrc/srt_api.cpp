@@ -611,6 +611,7 @@ void read_create_knobs(CreateKnobs &k) {
     read("SRT_LVL_SP", k.lvl_sp, as_int);
     read("SRT_LVL_DYN", k.lvl_dyn, as_int);
     read("SRT_LVL_PACK", k.lvl_pack, as_int);
+    read("SRT_LVL_CE4", k.lvl_ce4, as_int);
     read("SRT_LVL_SPREAD", k.lvl_spread, as_int);
     read("SRT_LVL_LEAN", k.lvl_lean, as_int);
     read("SRT_FW_P1", k.fw_p1, as_int);
@@ -978,6 +979,19 @@ srt_status choose_family(Create &c) {
                                                                         : (uint32_t)c.knobs.lvl_lean.v & srt::LVL_LEAN_ALL;
         p->desc = srt::describe_level(p->kp.g, p->lvl_q, p->kp.lmax, p->V, n, c.lvl_visits, p->lvl_sym,
                                       p->d_lat16 != nullptr, p->lvl_pack != 0);
+        // the packed row of a symmetric plan walks 4-byte class entries (its
+        // instantiation two workgroups a CU as well); whether every loss fits
+        // them is the first run's overflow word to say (ce4_off).  By default
+        // they ride with the packed row the plan chose itself: a row forced by
+        // SRT_LVL_PACK=1 is the A/B form that knob names, 8-byte entries, unless
+        // SRT_LVL_CE4=1 asks too
+        const bool want4 = c.knobs.lvl_ce4.set ? c.knobs.lvl_ce4.v != 0 : !c.knobs.lvl_pack.set;
+        p->lvl_ce4 = p->lvl_pack && p->lvl_sym && p->ident_rows && want4 &&
+                     srt::level_pack_fit(p->V, p->lvl_nt, true) >= 2;
+        if (p->lvl_ce4) {  // (beside the entries' other field, ahead of the rows' tokens)
+            const size_t at = p->desc.find(" loss=in-solve");
+            if (at != std::string::npos) p->desc.insert(at + 14, " ce=4");
+        }
     } else {
         p->lvl_q = 0;
         p->lvl_sym = p->lvl_sym_lat = false;
@@ -1474,6 +1488,10 @@ srt_status run_tail(srt_plan *p, srt_err *err) {
 }
 }  // namespace
 
+namespace {
+void ce4_off(srt_plan *p) { srt::level_ce4_off(p); }
+}  // namespace
+
 srt_status srt_plan_run_async(srt_plan *p, srt_err *err) {
     clear_err(err);
     if (!p) {
@@ -1504,8 +1522,17 @@ srt_status srt_plan_sync(srt_plan *p, srt_err *err) {
     if (p->algo != SRT_ALGO_SSSP && p->ev_loss0 && hipEventElapsedTime(&ms, p->ev_loss0, p->ev_loss1) == hipSuccess)
         p->loss_ms = ms;
     if (p->algo == SRT_ALGO_LEVEL && p->d_lvisit) {
-        unsigned long long v = 0;
-        if (hipMemcpy(&v, p->d_lvisit, sizeof v, hipMemcpyDeviceToHost) == hipSuccess) p->lvl_visits = v;
+        unsigned long long v[2] = {0, 0};  // the visit count and the 4-byte entries' overflow word
+        const bool got = hipMemcpy(v, p->d_lvisit, sizeof v, hipMemcpyDeviceToHost) == hipSuccess;
+        if (got) p->lvl_visits = v[0];
+        if (p->lvl_ce4_pending) {
+            if (!got) return hip_fail(err, hipGetLastError(), "level overflow word");
+            p->lvl_ce4_pending = false;
+            if (v[1]) {  // a loss did not fit: this table is wrong -- the run again, on 8-byte entries
+                ce4_off(p);
+                return srt_plan_run(p, err);
+            }
+        }
     }
     // in-process transport: what this rank received matched its senders'
     // checksums (srt_comm.cpp local_collective)
@@ -1532,8 +1559,19 @@ srt_status srt_plan_fetch(srt_plan *p, srt_path *out, uint64_t *min_latency_ns, 
     }
     HIP_TRY(hipSetDevice(p->device), "hipSetDevice");
     unsigned long long stats[2];
-    HIP_TRY(hipMemcpyAsync(stats, p->d_stats, sizeof stats, hipMemcpyDeviceToHost, p->stream), "stats");
-    HIP_TRY(hipStreamSynchronize(p->stream), "sync");
+    for (;;) {
+        // (a run on 4-byte class entries not synchronised yet: its overflow word rides along)
+        unsigned long long ovf = 0;
+        const bool pend = p->algo == SRT_ALGO_LEVEL && p->lvl_ce4_pending && p->d_lvisit;
+        if (pend) HIP_TRY(hipMemcpyAsync(&ovf, p->d_lvisit + 1, sizeof ovf, hipMemcpyDeviceToHost, p->stream), "overflow");
+        HIP_TRY(hipMemcpyAsync(stats, p->d_stats, sizeof stats, hipMemcpyDeviceToHost, p->stream), "stats");
+        HIP_TRY(hipStreamSynchronize(p->stream), "sync");
+        if (!pend) break;
+        p->lvl_ce4_pending = false;
+        if (!ovf) break;
+        ce4_off(p);  // the run again, on 8-byte entries
+        if (srt_status st = srt_plan_run_async(p, err); st != SRT_OK) return st;
+    }
     if (stats[1] != 0) {
         // the reference panics in assert_eq!(paths.len(), nodes.len().pow(2))
         // (mod.rs:219); this is Rust 1.76's assert_eq! panic message
@@ -1725,6 +1763,7 @@ srt_status srt_plan_bind_comm(srt_plan *p, srt_comm *comm, srt_err *err) {
         hipFree(p->d_rstats);
         p->d_rstats = (unsigned long long *)rs;
         p->comm = comm;
+        ce4_off(p);  // a comm-bound level plan exchanges 8-byte class entries
         p->row0 = std::min<uint32_t>(per * (uint32_t)comm->rank, p->n);
         p->row1 = std::min<uint32_t>(p->row0 + per, p->n);
         char d[64];

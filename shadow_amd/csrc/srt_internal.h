@@ -368,7 +368,11 @@ struct srt_plan {
     bool lvl_spread = true;                  // ... with K lane groups an item in small levels (knob SRT_LVL_SPREAD=0: one)
     uint32_t lvl_lean = srt::LVL_LEAN_KEPT;  // ... and these LVL_LEAN_* stages around the walk (knob SRT_LVL_LEAN=0: none)
     bool lvl_nt = true, lvl_sp = true, lvl_dyn = true;  // its launch knobs, read at create (CreateKnobs): LevelCtx::nt_store, sp, row_ctr
-    unsigned long long *d_lvisit = nullptr;  // level solve: class entries the last run walked
+    unsigned long long *d_lvisit = nullptr;  // level solve: [0] class entries the last run walked, [1] its 4-byte entries' overflow word
+    // 4-byte class entries v | (0x3f800000 - bits(1 - e)) << vb for the packed row's walk (knob SRT_LVL_CE4)
+    bool lvl_ce4 = false;          // the plan uses them (chosen at create; an overflowing run clears it for good)
+    bool lvl_ce4_run = false;      // the last class-CSR build wrote them (level_csr)
+    bool lvl_ce4_pending = false;  // ... and its overflow word has not been read yet (srt_plan_sync / srt_plan_fetch)
     uint32_t lvl_q = 0, lvl_rb = 0, lvl_vb = 0;  // quantized level solve: bucket width (units), entry field bits
     uint16_t *d_lmem = nullptr;              // its per-workgroup scratch (lmem_cap u16)
     uint64_t lmem_cap = 0;
@@ -534,6 +538,7 @@ struct LevelCtx {
     bool sp = true;                        // the pipelined class walk (false: the per-item walk)
     uint32_t pack = 0;                     // packed-row workgroups a CU (srt_plan::lvl_pack; 0: the unpacked row); needs lmem
     bool spread = true;                    // packed row: K lane groups an item in small levels
+    bool ce4 = false;                      // packed row: ce_out holds 4-byte entries (srt_plan::lvl_ce4_run)
     uint32_t lean = LVL_LEAN_KEPT;         // the LVL_LEAN_* stages around the walk (srt_plan::lvl_lean)
 };
 LevelCtx level_ctx(srt_plan *p);
@@ -552,7 +557,10 @@ size_t level_scratch_bytes(int device, uint32_t V, bool quant, uint32_t pack = 0
 // packed-row workgroups the runtime keeps resident on a CU of the current
 // device (the kernel's registers and its real dynamic LDS; 0: the query failed)
 int level_rows_per_cu(uint32_t V, bool quant, bool packed);
-int level_pack_fit(uint32_t V, bool nt_store);
+int level_pack_fit(uint32_t V, bool nt_store, bool ce4 = false);
+// a level plan leaves the 4-byte class entries for good (a loss did not fit
+// them, or its entries travel between ranks): ` ce=4` leaves its description
+void level_ce4_off(srt_plan *p);
 // bits of a vertex index < V in a quantized class entry
 uint32_t level_vbits(uint32_t V);
 // the shortest non-self-loop edge latency of the plan's uploaded graph, ns

@@ -59,7 +59,11 @@ constexpr int OUT_UNR = SRT_OUT_UNR;  // chunks of a row in flight a lane (pass 
 #define SRT_OUT_UNR16 8
 #endif
 constexpr int OUT_UNR16 = SRT_OUT_UNR16;  // ... of the u16 copy: 256-entry chunks (8 B a lane)
-template <bool WITH_LOSS, bool IN = true, bool IDENT = false, bool L16 = false>
+// CE4 (identity rows of symmetric plans with losses, exact classes): the 4-byte
+// entry v | (0x3f800000 - bits(1f32 - e)) << vb of the packed row's walk (vb:
+// the bits of V - 1); a hit whose difference needs more than 32 - vb bits sets
+// *ovf, and the run is repeated with 8-byte entries (level_run).
+template <bool WITH_LOSS, bool IN = true, bool IDENT = false, bool L16 = false, bool CE4 = false>
 __global__ __launch_bounds__(256) void lvl_out_kernel(uint32_t u0, uint32_t V, const uint64_t *__restrict__ row_ptr,
                                                       const uint32_t *__restrict__ col,
                                                       const uint64_t *__restrict__ lat, const float *__restrict__ loss,
@@ -68,8 +72,10 @@ __global__ __launch_bounds__(256) void lvl_out_kernel(uint32_t u0, uint32_t V, c
                                                       uint32_t *__restrict__ off_out, uint32_t *__restrict__ in_cnt,
                                                       uint64_t *__restrict__ ce_out, uint64_t cap,
                                                       unsigned long long *cursor, unsigned long long *maxw,
-                                                      const uint16_t *__restrict__ lat16 = nullptr) {
+                                                      const uint16_t *__restrict__ lat16 = nullptr,
+                                                      unsigned long long *ovf = nullptr) {
     static_assert(!L16 || (IDENT && !IN), "the u16 copy: identity rows of symmetric plans");
+    static_assert(!CE4 || (IDENT && !IN && WITH_LOSS), "4-byte entries: out-rows of symmetric plans, with losses");
     __shared__ uint32_t stage[4][OUT_SCAP];  // per wave: place in the row | units << 16 (0xffff: read again) of hit j
     __shared__ uint32_t ccnt[4][64];      // per wave: hits per class (pass 1), running positions (pass 2)
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -163,6 +169,12 @@ __global__ __launch_bounds__(256) void lvl_out_kernel(uint32_t u0, uint32_t V, c
             const float eb = WITH_LOSS ? 1.0f - ls : 0.0f;  // (1f32 - other.packet_loss), mod.rs:328
             // q > 0 (quantized classes): the weight's remainder w - c q rides
             // along, (1 - e) in bits 34.. (a loss in [0, 1]: its bits are < 2^30)
+            if constexpr (CE4) {
+                // (a loss outside [0, 1] or a NaN wraps the difference past every field: it overflows too)
+                const uint32_t d = 0x3f800000u - __float_as_uint(eb);
+                if (d >> (32u - vb)) atomicOr(ovf, 1ull);
+                reinterpret_cast<uint32_t *>(ce_out)[pos] = v | d << vb;
+            } else
             ce_out[pos] = q ? ((uint64_t)__float_as_uint(eb) << 34) | ((wu - (uint64_t)cl * q) << vb) | v
                             : ((uint64_t)__float_as_uint(eb) << 32) | v;
             if (IN) atomicAdd(&in_cnt[(uint64_t)v * cls + cl - 1], 1u);  // symmetric plans: no in-rows
@@ -465,8 +477,14 @@ static_assert(WAVE_U >= 1 && WAVE_D % WAVE_U == 0, "the ring is folded in whole 
 // state 0 and writes their 4-bit levels, a thread the word of its own quad
 // (plain stores); the members go to mem_all + blockIdx.x * V (L2-resident, as
 // level_q_kernel's).  spread: K lane groups an item in small levels (below).
-template <int LPT, int UNR, uint32_t CLSN, int VW, bool NT, bool SP = false, bool PK = false>
-__global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
+// CE4 (PK; level_ce4_kernel): the class entries are the 4-byte form of
+// lvl_out_kernel<..., CE4>, at the same indices; every walker decodes v = x &
+// mask, bits(1 - e) = 0x3f800000 - (x >> vb), the 8-byte entry's fields bit for
+// bit.
+// The body is shared: level_solve_kernel runs it on 8-byte entries,
+// level_ce4_kernel (the packed row alone) on 4-byte ones.
+template <int LPT, int UNR, uint32_t CLSN, int VW, bool NT, bool SP, bool PK, bool CE4>
+__device__ __forceinline__ void level_solve_body(
     uint32_t V, const uint32_t *__restrict__ nodes, uint32_t n, uint32_t row0, uint32_t row1,
     const uint32_t *__restrict__ cls_out, const uint32_t *__restrict__ cls_in, const uint64_t *__restrict__ ce_out,
     const uint64_t *__restrict__ ce_in, uint32_t lcap, uint64_t g, const uint64_t *__restrict__ sl_lat,
@@ -474,8 +492,12 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
     unsigned long long *stats, const uint32_t *__restrict__ row_list, void *__restrict__ out32,
     float *__restrict__ out32_loss, bool stage16, uint32_t *__restrict__ probe,
     unsigned long long *__restrict__ visit_cnt, bool idn, unsigned long long *row_ctr, uint16_t *mem_all,
-    bool spread, uint32_t lean) {
+    bool spread, uint32_t lean, uint32_t vb) {
     static_assert(!PK || (SP && CLSN == 16), "the packed row: the pipelined walk, levels <= PACK_LMAX");
+    static_assert(!CE4 || PK, "4-byte class entries: the packed row's walks");
+    const uint32_t vmask4 = (1u << vb) - 1u;  // CE4: an entry's vertex bits
+    // CE4: a 4-byte entry as the 8-byte one's halves (.x the vertex, .y the bits of 1 - e)
+    auto dec4 = [&](uint32_t xw) -> uint2 { return make_uint2(xw & vmask4, 0x3f800000u - (xw >> vb)); };
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ unsigned long long red_min[16], red_cnt[16], red_vis[16];
     __shared__ uint32_t dyn_k;
@@ -728,9 +750,14 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                     vis32 += ls == 0 ? e1 - e0 : 0u;
                     const float onem = 1.0f - __uint_as_float(key[x] & PACK_LOSS);
                     for (uint32_t e = e0 + ls; e < e1; e += LIST_LPI) {
-                        const uint64_t wd = ce_out[e];
-                        const uint32_t o = (uint32_t)wd;
-                        const uint32_t b = __float_as_uint(1.0f - __fmul_rn(onem, __uint_as_float((uint32_t)(wd >> 32))));
+                        uint2 wd;
+                        if constexpr (CE4) {
+                            wd = dec4(reinterpret_cast<const uint32_t *>(ce_out)[e]);
+                        } else {
+                            wd = reinterpret_cast<const uint2 *>(ce_out)[e];
+                        }
+                        const uint32_t o = wd.x;
+                        const uint32_t b = __float_as_uint(1.0f - __fmul_rn(onem, __uint_as_float(wd.y)));
                         if (key[o] > PACK_LOSS && atomicMin(&key[o], 1u << 30 | (b & PACK_LOSS)) >= 3u << 30)
                             mem[settled + atomicAdd(&cur[par][1], 1u)] = (uint16_t)o;
                     }
@@ -792,7 +819,7 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                     const uint32_t pb = (uint32_t)__shfl(e0, it) + 64u * j, pr = il - 64u * j;
                     const uint32_t pom = __shfl(__float_as_uint(onem), it);
                     const uint32_t nq = total - win < 64u ? total - win : 64u;
-                    uint2 ring[D];
+                    typename std::conditional<CE4, uint32_t, uint2>::type ring[D];  // (CE4: one register a pass)
                     uint32_t rrem[D], rom[D];  // a ring slot's entries (0: none) and 1 - loss, uniform
                     auto issue = [&](int r, uint32_t q) {
                         const uint32_t qc = q < nq ? q : nq - 1u;
@@ -800,7 +827,19 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                         rrem[r] = q < nq ? rm : 0u;
                         rom[r] = (uint32_t)__builtin_amdgcn_readlane(pom, qc);
                         const uint32_t o = (uint32_t)lane < rm - 1u ? (uint32_t)lane : rm - 1u;
-                        ring[r] = reinterpret_cast<const uint2 *>(ce_out + (uint32_t)__builtin_amdgcn_readlane(pb, qc))[o];
+                        const uint32_t pq = (uint32_t)__builtin_amdgcn_readlane(pb, qc);
+                        if constexpr (CE4) {
+                            ring[r] = reinterpret_cast<const uint32_t *>(ce_out)[pq + o];  // 256 B a pass
+                        } else {
+                            ring[r] = reinterpret_cast<const uint2 *>(ce_out + pq)[o];
+                        }
+                    };
+                    auto entry = [&](int r) -> uint2 {
+                        if constexpr (CE4) {
+                            return dec4(ring[r]);
+                        } else {
+                            return ring[r];
+                        }
                     };
 #pragma unroll
                     for (int r = 0; r < D; ++r) issue(r, r);
@@ -812,11 +851,11 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
 #if SRT_PK_PROBE
                             uint32_t ko[U];
 #pragma unroll
-                            for (int u = 0; u < U; ++u) ko[u] = key[ring[r0 + u].x];
+                            for (int u = 0; u < U; ++u) ko[u] = key[entry(r0 + u).x];
 #endif
 #pragma unroll
                             for (int u = 0; u < U; ++u) {
-                                const uint2 wd = ring[r0 + u];
+                                const uint2 wd = entry(r0 + u);
                                 const uint32_t b = __float_as_uint(1.0f - __fmul_rn(__uint_as_float(rom[r0 + u]), __uint_as_float(wd.y)));
 #if SRT_PK_PROBE
                                 if ((uint32_t)lane < rrem[r0 + u] && ko[u] > PACK_LOSS)
@@ -843,10 +882,18 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                 static_assert(VW == 2, "the pipelined walk loads entry pairs");
                 constexpr uint32_t CH = UNR * LPT * 2;
                 constexpr int NE = UNR * 2;
-                auto load = [&](uint4 *d, uint32_t w, uint32_t b) {
+                // (CE4: an entry pair is 8 B, the even entry 8-B aligned)
+                typedef typename std::conditional<CE4, uint2, uint4>::type pair_t;
+                auto load = [&](pair_t *d, uint32_t w, uint32_t b) {
                     const uint64_t *ce = ((pm >> w) & 1ull) ? ce_out : ce_in;
 #pragma unroll
-                    for (int q = 0; q < UNR; ++q) d[q] = *reinterpret_cast<const uint4 *>(ce + b + (sub + q * LPT) * 2);
+                    for (int q = 0; q < UNR; ++q) {
+                        if constexpr (CE4) {
+                            d[q] = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint32_t *>(ce) + b + (sub + q * LPT) * 2);
+                        } else {
+                            d[q] = *reinterpret_cast<const uint4 *>(ce + b + (sub + q * LPT) * 2);
+                        }
+                    }
                 };
                 // a small level (2 T <= lane groups) in a workgroup alone on its
                 // CU (1,024 threads: nothing else hides its latency): K groups an
@@ -864,7 +911,7 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                 pw = cw;
                 if (ct + ngrp < T) item(ct + ngrp, pw, px, pe0, pe1);
                 uint32_t cb = (ce0 & ~1u) + (K > 1 ? grp / T : 0u) * CH;
-                uint4 cur[UNR];
+                pair_t cur[UNR];
                 if (ct < T && cb < ce1) load(cur, cw, cb);  // (a chunk past a short list: nothing to load)
                 while (ct < T) {
                     // the next chunk: this item's next one, or the next item's first
@@ -878,7 +925,7 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                         ne12 = pe1;
                         nb = pe0 & ~1u;
                     }
-                    uint4 nxt[UNR];
+                    pair_t nxt[UNR];
                     if (nt2 < T) load(nxt, nw2, nb);
                     if (adv && nt2 + ngrp < T) item(nt2 + ngrp, pw, px, pe0, pe1);
                     if (cb < ce1) {
@@ -893,8 +940,14 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
                         const int32_t s_lo = (int32_t)(ce0 - a0), s_hi = (int32_t)(ce1 - a0);
 #pragma unroll
                         for (int q = 0; q < UNR; ++q) {
-                            wd[2 * q] = ((uint64_t)cur[q].y << 32) | cur[q].x;
-                            wd[2 * q + 1] = ((uint64_t)cur[q].w << 32) | cur[q].z;
+                            if constexpr (CE4) {
+                                const uint2 a = dec4(cur[q].x), c = dec4(cur[q].y);
+                                wd[2 * q] = ((uint64_t)a.y << 32) | a.x;
+                                wd[2 * q + 1] = ((uint64_t)c.y << 32) | c.x;
+                            } else {
+                                wd[2 * q] = ((uint64_t)cur[q].y << 32) | cur[q].x;
+                                wd[2 * q + 1] = ((uint64_t)cur[q].w << 32) | cur[q].z;
+                            }
                             ok[2 * q] = 2 * LPT * q < s_hi && (q > 0 || s_lo <= 0);
                             ok[2 * q + 1] = 2 * LPT * q + 1 < s_hi;
                         }
@@ -1268,6 +1321,39 @@ __global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
     }
 }
 
+template <int LPT, int UNR, uint32_t CLSN, int VW, bool NT, bool SP = false, bool PK = false>
+__global__ __launch_bounds__(LOSS_NT) void level_solve_kernel(
+    uint32_t V, const uint32_t *__restrict__ nodes, uint32_t n, uint32_t row0, uint32_t row1,
+    const uint32_t *__restrict__ cls_out, const uint32_t *__restrict__ cls_in, const uint64_t *__restrict__ ce_out,
+    const uint64_t *__restrict__ ce_in, uint32_t lcap, uint64_t g, const uint64_t *__restrict__ sl_lat,
+    const float *__restrict__ sl_loss, uint64_t *__restrict__ out_lat, float *__restrict__ out_loss,
+    unsigned long long *stats, const uint32_t *__restrict__ row_list, void *__restrict__ out32,
+    float *__restrict__ out32_loss, bool stage16, uint32_t *__restrict__ probe,
+    unsigned long long *__restrict__ visit_cnt, bool idn, unsigned long long *row_ctr, uint16_t *mem_all,
+    bool spread, uint32_t lean) {
+    level_solve_body<LPT, UNR, CLSN, VW, NT, SP, PK, false>(V, nodes, n, row0, row1, cls_out, cls_in, ce_out, ce_in, lcap, g,
+                                                            sl_lat, sl_loss, out_lat, out_loss, stats, row_list, out32,
+                                                            out32_loss, stage16, probe, visit_cnt, idn, row_ctr, mem_all,
+                                                            spread, lean, 0u);
+}
+
+// The packed row on 4-byte class entries (vb: the bits of V - 1): the packed
+// instantiation's arguments and the entry's vertex bits.
+template <bool NT>
+__global__ __launch_bounds__(LOSS_NT) void level_ce4_kernel(
+    uint32_t V, const uint32_t *__restrict__ nodes, uint32_t n, uint32_t row0, uint32_t row1,
+    const uint32_t *__restrict__ cls_out, const uint32_t *__restrict__ cls_in, const uint64_t *__restrict__ ce_out,
+    const uint64_t *__restrict__ ce_in, uint32_t lcap, uint64_t g, const uint64_t *__restrict__ sl_lat,
+    const float *__restrict__ sl_loss, uint64_t *__restrict__ out_lat, float *__restrict__ out_loss,
+    unsigned long long *stats, const uint32_t *__restrict__ row_list, void *__restrict__ out32,
+    float *__restrict__ out32_loss, bool stage16, uint32_t *__restrict__ probe,
+    unsigned long long *__restrict__ visit_cnt, bool idn, unsigned long long *row_ctr, uint16_t *mem_all,
+    bool spread, uint32_t lean, uint32_t vb) {
+    level_solve_body<4, 4, 16, 2, NT, true, true, true>(V, nodes, n, row0, row1, cls_out, cls_in, ce_out, ce_in, lcap, g, sl_lat,
+                                                        sl_loss, out_lat, out_loss, stats, row_list, out32, out32_loss,
+                                                        stage16, probe, visit_cnt, idn, row_ctr, mem_all, spread, lean, vb);
+}
+
 // ------------------------------------------------- quantized level solve
 // The level solve for latencies that are not small integers of g (Shadow
 // reads any unit down to ns, units.rs:377-388: C3ns has g = 1 ns and edges of
@@ -1584,13 +1670,15 @@ __global__ __launch_bounds__(256) void edge_min_kernel(uint32_t V, const uint64_
 // the level build's per-run counters in one launch (small memsets are a
 // ~4.6 us fill kernel each on the device timeline): stats, the class max,
 // the visit count; or (stats == nullptr) the class-CSR pass's cursor and max
-__global__ void level_zero_kernel(unsigned long long *stats, unsigned long long *a, unsigned long long *b) {
+__global__ void level_zero_kernel(unsigned long long *stats, unsigned long long *a, unsigned long long *b,
+                                  unsigned long long *c = nullptr) {
     if (stats) {
         stats[0] = ~0ull;
         stats[1] = 0ull;
     }
     if (a) *a = 0ull;
     if (b) *b = 0ull;
+    if (c) *c = 0ull;
 }
 
 }  // namespace
@@ -1621,6 +1709,7 @@ LevelCtx level_ctx(srt_plan *p) {
     c.sp = p->lvl_sp;
     c.pack = p->lvl_pack;
     c.spread = p->lvl_spread;
+    c.ce4 = p->lvl_ce4_run;
     // (the packed row's listed levels: LIST_T items at most; SRT_LVL_LIST_T: fewer, A/B)
     const char *lt = std::getenv("SRT_LVL_LIST_T");
     const uint32_t list_t = std::min<uint32_t>(lt ? (uint32_t)std::atoi(lt) : LIST_T, LIST_T);
@@ -1637,6 +1726,12 @@ LevelCtx level_ctx(srt_plan *p) {
     }
     c.row_ctr = dyn ? p->d_rowctr : nullptr;
     return c;
+}
+
+void level_ce4_off(srt_plan *p) {
+    p->lvl_ce4 = p->lvl_ce4_pending = false;
+    const size_t at = p->desc.find(" ce=4");
+    if (at != std::string::npos) p->desc.erase(at, 5);
 }
 
 uint32_t level_vbits(uint32_t V) {
@@ -1666,16 +1761,20 @@ srt_status level_csr_arrays(srt_plan *p, uint64_t vc1, srt_err *err) {
 // identity rows of a symmetric plan (out-rows only: no in-row counts), l16 =
 // they read the u16-unit copy p->d_lat16.  Class offsets to `offsets`, entries
 // to `entries` (slots below `cap`, from the cursor's value on).
+// ce4: the 4-byte entries of the packed row's walk (ident, with_loss, q = 0; vb = level_vbits(V)), overflow word
+// p->d_lvisit[1].
 void launch_lvl_out(srt_plan *p, bool with_loss, bool ident, bool l16, uint32_t u0, uint32_t u1, uint64_t wns,
-                    uint32_t cls, uint32_t q, uint32_t vb, uint32_t *offsets, uint64_t *entries, uint64_t cap) {
-    const auto kern = !ident ? (with_loss ? lvl_out_kernel<true> : lvl_out_kernel<false>)
+                    uint32_t cls, uint32_t q, uint32_t vb, uint32_t *offsets, uint64_t *entries, uint64_t cap,
+                    bool ce4 = false) {
+    const auto kern = ce4    ? (l16 ? lvl_out_kernel<true, false, true, true, true> : lvl_out_kernel<true, false, true, false, true>)
+                      : !ident ? (with_loss ? lvl_out_kernel<true> : lvl_out_kernel<false>)
                       : l16  ? (with_loss ? lvl_out_kernel<true, false, true, true> : lvl_out_kernel<false, false, true, true>)
                              : (with_loss ? lvl_out_kernel<true, false, true> : lvl_out_kernel<false, false, true>);
     const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(8192, (u1 - u0 + 3) / 4));
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, p->stream, u0, u1, p->d_row_ptr, p->d_col, p->d_lat,
                        with_loss ? p->d_loss : (const float *)nullptr, p->kp.g, 1.0 / (double)p->kp.g, wns, cls, q, vb,
                        offsets, p->d_tccnt, entries, cap, p->d_tcursor, (unsigned long long *)p->d_tmaxw,
-                       l16 ? p->d_lat16 : (const uint16_t *)nullptr);
+                       l16 ? p->d_lat16 : (const uint16_t *)nullptr, ce4 ? p->d_lvisit + 1 : (unsigned long long *)nullptr);
 }
 
 // The class CSRs of the graph's edges of latency <= wmax units (self-loops
@@ -1685,10 +1784,13 @@ void launch_lvl_out(srt_plan *p, bool with_loss, bool ident, bool l16, uint32_t 
 // the first call (the create-time probe, wmax = min(31, max edge)) counts,
 // sizes them and runs again; every later call prunes at the probe's bound <=
 // that wmax, so its count fits and nothing waits for the host.
-srt_status level_csr(srt_plan *p, uint64_t wmax, bool with_loss, srt_err *err) {
+// ce4: a symmetric plan's out-rows as 4-byte entries (the packed row's run; the
+// overflow word p->d_lvisit[1] is zeroed with the cursor) -- p->lvl_ce4_run says
+// whether this build wrote them.
+srt_status level_csr(srt_plan *p, uint64_t wmax, bool with_loss, srt_err *err, bool ce4 = false) {
     hipStream_t M = p->stream;
     const uint32_t V = p->V;
-    const uint32_t q = p->lvl_q, vb = q ? p->lvl_vb : 32u;
+    const uint32_t q = p->lvl_q;
     const uint64_t ncls = q ? wmax / q : wmax;
     const uint32_t cls = ncls < 16 ? 16 : ncls < 32 ? 32 : 64;
     const uint64_t vc1 = (uint64_t)V * cls + 1;
@@ -1704,14 +1806,19 @@ srt_status level_csr(srt_plan *p, uint64_t wmax, bool with_loss, srt_err *err) {
     // their losses too when the entries carry them): out-rows only
     const bool single = with_loss ? p->lvl_sym : p->lvl_sym_lat;
     p->lvl_single = single;
+    const bool use4 = ce4 && single && with_loss && !q && p->d_lvisit;
+    p->lvl_ce4_run = use4;
+    const uint32_t vb = q ? p->lvl_vb : use4 ? level_vbits(V) : 32u;
     auto out_pass = [&]() {
         if (!single)  // in-row counts, then in-row cursors (out-rows-only plans count none)
             (void)hipMemsetAsync(p->d_tccnt, 0, 2 * vc1 * 4, M);
         hipLaunchKernelGGL(level_zero_kernel, dim3(1), dim3(1), 0, M, (unsigned long long *)nullptr,
-                           (unsigned long long *)p->d_tcursor, (unsigned long long *)p->d_tmaxw);
+                           (unsigned long long *)p->d_tcursor, (unsigned long long *)p->d_tmaxw,
+                           use4 ? p->d_lvisit + 1 : (unsigned long long *)nullptr);
         // symmetric plans have identity rows (lvl_sym_tile_kernel); theirs may read
         // the u16-unit copy (the symmetry check's; wmax < 0xffff units)
-        launch_lvl_out(p, with_loss, single, single && p->d_lat16, 0u, V, wns, cls, q, vb, p->d_tcls, p->d_tpk, p->lvl_cap);
+        launch_lvl_out(p, with_loss, single, single && p->d_lat16, 0u, V, wns, cls, q, vb, p->d_tcls, p->d_tpk, p->lvl_cap,
+                       use4);
     };
     // first call (the create-time probe): entry arrays of the caller's
     // estimate (p->lvl_est; +1024: the solve's 2-entry loads read up to UNR *
@@ -1861,6 +1968,7 @@ srt_status level_csr_sharded(srt_plan *p, uint64_t wmax, bool with_loss, uint32_
     cspan_end(p);
     if (e != hipSuccess) return fail(err, e, "class offsets (sharded)");
     p->lvl_single = true;
+    p->lvl_ce4_run = false;  // the slice exchange moves 8-byte entries
     p->t_cls = cls;
     p->t_q = 1;
     p->t_level = true;
@@ -1872,6 +1980,8 @@ srt_status level_csr_sharded(srt_plan *p, uint64_t wmax, bool with_loss, uint32_
 auto pick_packed_kernel(bool nt_store) {
     return nt_store ? level_solve_kernel<4, 4, 16, 2, true, true, true> : level_solve_kernel<4, 4, 16, 2, false, true, true>;
 }
+// ... on 4-byte class entries
+auto pick_ce4_kernel(bool nt_store) { return nt_store ? level_ce4_kernel<true> : level_ce4_kernel<false>; }
 
 // Workgroups of a level solve launch over `rows` rows (one row per
 // workgroup at a time; the LDS row decides how many fit a CU)
@@ -1954,6 +2064,15 @@ void launch_solve_ctx(const LevelCtx &c, unsigned long long *d_stats, const uint
         hipLaunchKernelGGL(kern, dim3(grid), dim3(nt), lds, c.stream, V, c.nodes, c.n, list ? 0u : r0, r1, co, ci,
                            eo, ei, kcap, lcap, c.q, c.rb, c.vb, c.g, c.sl_lat, c.sl_loss, c.out_lat, c.out_loss, d_stats,
                            list, stage, stage_loss, stage_mode, probe, c.visits, c.lmem);
+        return;
+    }
+    if (pack && c.ce4) {  // (4-byte entries are written only for a run on the packed row: level_run)
+        const auto k4 = pick_ce4_kernel(c.nt_store);
+        (void)hipFuncSetAttribute((const void *)k4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BUDGET - 4096));
+        hipLaunchKernelGGL(k4, dim3(grid), dim3(nt), lds, c.stream, V, c.nodes, c.n, list ? 0u : r0, r1, co, ci, eo, ei, lcap,
+                           c.g, c.sl_lat, c.sl_loss, c.out_lat, c.out_loss, d_stats, list, stage_mode ? stage : nullptr,
+                           stage_mode ? stage_loss : nullptr, stage_mode == 1, probe, c.visits, c.idn, c.row_ctr, c.lmem,
+                           c.spread, c.lean, level_vbits(V));
         return;
     }
     const auto kern = pack ? pick_packed_kernel(c.nt_store) : pick_solve_kernel(c.t_cls, c.nt_store, c.sp);
@@ -2113,10 +2232,10 @@ size_t level_scratch_bytes(int device, uint32_t V, bool quant, uint32_t pack) {
     return quant || pack ? (size_t)level_grid(device, V, quant, ~0u, nullptr, quant ? 0u : pack) * V * 2 : 0;
 }
 
-int level_pack_fit(uint32_t V, bool nt_store) {
-    const auto kern = pick_packed_kernel(nt_store);
+int level_pack_fit(uint32_t V, bool nt_store, bool ce4) {
+    const void *kern = ce4 ? (const void *)pick_ce4_kernel(nt_store) : (const void *)pick_packed_kernel(nt_store);
     int wgs = 0;
-    if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BUDGET - 4096)) !=
+    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BUDGET - 4096)) !=
             hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, kern, (int)PACK_NT, solve_lds_bytes(V, false, true)) !=
             hipSuccess) {
@@ -2224,6 +2343,19 @@ srt_status level_run(srt_plan *p, unsigned long long *d_stats, srt_err *err) {
     // sharded too (level_csr_sharded); the others build it whole
     const bool sym_int = p->lvl_sym && !p->lvl_q && p->ident_rows;
     srt_status st;
+    if (!p->d_lvisit) {  // [0] the visit count, [1] the 4-byte entries' overflow word
+        const hipError_t e = hipMalloc(&p->d_lvisit, 2 * sizeof(unsigned long long));
+        if (e != hipSuccess) return fail(err, e, "hipMalloc(visit counter)");
+        (void)hipMemsetAsync(p->d_lvisit, 0, 2 * sizeof(unsigned long long), p->stream);
+    }
+    // 4-byte class entries: a plan that chose them (lvl_ce4), its rows on the
+    // packed row (launch_solve_ctx's conditions) and read where they are built --
+    // not exchanged between ranks, nor downloaded behind the solve (the repeat
+    // after an overflow is srt_plan_sync's and srt_plan_fetch's)
+    const bool ce4 = p->lvl_ce4 && sym_int && p->lvl_pack && p->lvl_sp && p->kp.lmax <= PACK_LMAX && !p->comm &&
+                     !p->fold_chunk_rows;
+    if (sym_int && ((p->comm && p->comm->nranks > 1) || (p->row_shard && p->lvl_emu_ranks > 1)))
+        level_ce4_off(p);  // the sharded class CSR exchanges 8-byte entries
     if (sym_int && p->comm && p->comm->nranks > 1)
         st = level_csr_sharded(p, p->kp.lmax, true, (uint32_t)p->comm->nranks, (uint32_t)p->comm->rank, p->comm, err);
     else if (sym_int && p->row_shard && p->lvl_emu_ranks > 1)
@@ -2231,12 +2363,9 @@ srt_status level_run(srt_plan *p, unsigned long long *d_stats, srt_err *err) {
                                (uint32_t)((uint64_t)p->row0 * p->lvl_emu_ranks / std::max<uint32_t>(p->n, 1)), nullptr,
                                err);
     else
-        st = level_csr(p, p->kp.lmax, true, err);
+        st = level_csr(p, p->kp.lmax, true, err, ce4);
     if (st != SRT_OK) return st;
-    if (!p->d_lvisit) {
-        const hipError_t e = hipMalloc(&p->d_lvisit, sizeof(unsigned long long));
-        if (e != hipSuccess) return fail(err, e, "hipMalloc(visit counter)");
-    }
+    p->lvl_ce4_pending = p->lvl_ce4_run;
     hipLaunchKernelGGL(level_zero_kernel, dim3(1), dim3(1), 0, p->stream, d_stats, (unsigned long long *)p->d_tmaxw,
                        p->d_lvisit);
 #if LOSS_COUNT

@@ -328,6 +328,10 @@ srt_status packet_round(srt_plan *plan, const srt_pkt *d_pkts, const uint32_t *d
         perr(err, SRT_ERR_INVALID, "routing table not built (run the plan first)");
         return SRT_ERR_INVALID;
     }
+    // a level build on 4-byte class entries nobody has synchronised yet: its
+    // overflow word is read (and the build repeated on 8-byte entries) first
+    if (plan->lvl_ce4_pending)
+        if (srt_status st = srt_plan_sync(plan, err); st != SRT_OK) return st;
     if (plan->row_shard || plan->row0 != 0 || plan->row1 != plan->n) {
         perr(err, SRT_ERR_INVALID, "the packet stage needs the whole table on the plan's device");
         return SRT_ERR_INVALID;
