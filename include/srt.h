@@ -544,9 +544,9 @@ void srt_inbound_destroy(srt_inbound *ib);
  * close, say); a caller that disassociates a socket mid-window must treat the
  * window's later deliveries to that socket as the lookup would, or split the
  * window there.
- * OUT OF SCOPE: pcap capture, what the socket does with the packet, the
- * loopback relay, the CPU-delay model.  (The tracker's byte counts of the
- * internet interface are the srt_tracker stage below.)
+ * OUT OF SCOPE: what the socket does with the packet, the loopback relay, the
+ * CPU-delay model.  (The tracker's byte counts of the internet interface are
+ * the srt_tracker stage below, pcap capture the srt_pcap stage.)
  * ABI: additive to version 4; detect the stage by its symbols. */
 typedef struct srt_deliver srt_deliver;
 
@@ -948,8 +948,8 @@ void srt_sendbatch_destroy(srt_sendbatch *sb);
  * The reference orders a heartbeat task and a packet event of the same instant
  * by event id, which the library does not own.
  * The LOCAL counters are the loopback interface's: srt_loopback below.
- * OUT OF SCOPE: the tracker's CPU, memory and socket-buffer lines, pcap
- * capture.
+ * OUT OF SCOPE: the tracker's CPU, memory and socket-buffer lines.  (pcap
+ * capture, at the same two points, is the srt_pcap stage below.)
  * ABI: additive to version 4; detect the stage by its symbols. */
 typedef struct srt_tracker srt_tracker;
 
@@ -1221,6 +1221,142 @@ srt_status srt_loopback_tasks(srt_loopback *lb, uint64_t *out_tasks, srt_err *er
 srt_status srt_loopback_status(srt_loopback *lb, uint32_t *flags, uint64_t *n_received, uint64_t *n_no_socket,
                                srt_err *err);
 void srt_loopback_destroy(srt_loopback *lb);
+
+/* ------------------------------------------------------------ pcap capture */
+/* The packet capture a host switches on with pcap_enabled / pcap_capture_size
+ * (core/configuration.rs:558-577), built on the device: one byte stream a host,
+ * the body of the file the reference's PcapWriter writes for an interface
+ * (utility/pcap_writer.rs).  The capture points are the tracker's:
+ * networkinterface_pop captures a packet right after SND_INTERFACE_SENT
+ * (host/network/network_interface.c:310-340), networkinterface_push before the
+ * socket hand-off, whether or not a socket takes the packet (:140-202).  One
+ * instance is one interface class: a caller that captures the loopback
+ * interfaces too makes a second instance.
+ * A record is 16 + incl_len bytes (pcap_writer.rs:86-142,
+ * network_interface.c:119-134), the header native endian:
+ *   ts_sec  u32 = time_ns / 10^9          ts_usec  u32 = (time_ns % 10^9) / 1000
+ *   incl_len u32 = min(capture_len, total)  orig_len u32 = total
+ * with total = header_size + payload_len and header_size 28 for UDP, 40 for TCP,
+ * 44 for TCP with the window-scale option (packet_getHeaderSize,
+ * routing/packet.c:378-403, plus the 20-byte IP header).  Then the first
+ * incl_len bytes of the packet as network/packet.rs:374-586 displays it, all
+ * big endian.  IP: 45 00, total u16, id 00 00, 40 00, TTL 40, protocol, checksum
+ * 00 00, source, destination.  TCP: ports, seq, ack (0 when ACK is not set),
+ * the data-offset byte ((20 + options) / 4) << 4, the flag byte (tcp_flags &
+ * 0x17: FIN 0x01, SYN 0x02, RST 0x04, ACK 0x10), window u16, checksum 0, urgent
+ * 0, and with wscale_set the option 03 03 <wscale> 00.  UDP: ports, payload_len
+ * + 8 as u16, checksum 0.  Then the payload.  The cut is at exactly capture_len
+ * bytes (utility/give.rs), in the middle of a field or of the IP header if it
+ * falls there; capture_len 0 leaves the 16-byte record header alone.
+ * LIMIT: a host's sent and received packets of the same instant.  The reference
+ * writes them in the order their events run, packet events before local ones
+ * (core/work/event.rs:102-110), which is SRT_PCAP_RX_FIRST, the default; the
+ * exact order at one instant depends on event ids, which the library does not
+ * own (the tracker's caveat).  SRT_PCAP_TX_FIRST is the other choice.
+ * ABI: additive to version 4; detect the stage by its symbols. */
+typedef struct srt_pcap srt_pcap;
+
+/* what the capture needs of a packet, 48 bytes */
+typedef struct {
+    uint64_t time_ns;     /* simulation time of the pop or the push */
+    uint64_t payload_off; /* the payload's first byte in d_payload */
+    uint32_t src_ip_be;   /* network byte order, as the IP assignment passes addresses */
+    uint32_t dst_ip_be;
+    uint16_t src_port_be; /* network byte order */
+    uint16_t dst_port_be;
+    uint32_t seq;         /* TCP, host order, as are ack and window */
+    uint32_t ack;         /* written as 0 unless tcp_flags has ACK */
+    uint16_t window;
+    uint16_t payload_len;
+    uint8_t protocol;     /* 6 TCP, 17 UDP */
+    uint8_t tcp_flags;    /* wire bits; only 0x17 is used */
+    uint8_t wscale;
+    uint8_t wscale_set;   /* the window-scale option is present */
+    uint32_t reserved;
+} srt_pcap_rec;
+
+#define SRT_PCAP_RX_FIRST 0u /* srt_pcap_create flags: at equal times a host's received packets come first */
+#define SRT_PCAP_TX_FIRST 1u /* its sent packets come first */
+
+#define SRT_PCAP_OVERFLOW     1u  /* the call's bytes exceed out_cap: d_host_off written, d_out untouched */
+#define SRT_PCAP_BAD_PROTOCOL 2u  /* protocol neither 6 nor 17: skipped, 0 bytes */
+#define SRT_PCAP_BAD_LENGTH   4u  /* header_size + payload_len > 65535: skipped */
+#define SRT_PCAP_BAD_PAYLOAD  8u  /* payload_off + payload_len > payload_bytes: skipped */
+#define SRT_PCAP_TIME_ORDER   16u /* a list decreases within a host, or starts before the host's last record */
+
+/* An instance for n_hosts hosts on the plan's device and stream, or, with
+ * plan == NULL, host-only: every array argument named d_ is then a HOST pointer
+ * and the calls complete before they return.  Both forms run the same step and
+ * agree byte for byte.  capture_len is the snap length of every host; enabled
+ * (HOST pointer, n_hosts bytes, copied) says which hosts capture, NULL: all.
+ * rec_cap bounds n_tx + n_rx of a call; flags is SRT_PCAP_RX_FIRST or
+ * SRT_PCAP_TX_FIRST.  Memory of the instance, in bytes:
+ *   40 + n_hosts * 32 + rec_cap * 16
+ * (the state words; per host the last time, the call's largest time, its bytes,
+ * its record count and the enabled byte; per record of a call its list entry,
+ * size and byte offset), on the device.  Nothing is allocated per call.
+ * n_hosts and rec_cap are below 2^31.  Destroy the instance before its plan. */
+srt_status srt_pcap_create(srt_plan *plan, uint32_t n_hosts, uint32_t capture_len, const uint8_t *enabled,
+                           uint64_t rec_cap, uint32_t flags, srt_pcap **out, srt_err *err);
+
+/* One call formats the packets hosts sent (d_tx) and received (d_rx) in a span
+ * of time.  Each list is grouped by host through a pointer array of n_hosts + 1
+ * entries (ptr[0] == 0, nondecreasing), as every stage takes its batches, and is
+ * nondecreasing in time_ns within a host.  d_*_idx is an optional indirection:
+ * entry k of the list is d_tx[d_tx_idx[k]] (NULL: d_tx[k]), so srt_outbound's
+ * send order or srt_deliver's output order is handed over without a gather; the
+ * caller guarantees that every index names a record of its array.  n_tx and
+ * n_rx may be the capacity of the lists: the walk is bounded by
+ * min(ptr[n_hosts], n) on the device, so nothing is read back before the call.
+ * n_tx + n_rx <= rec_cap.
+ * Per host the two lists are merged stably by time_ns, equal times by the
+ * create-time flag; every record becomes 16 + incl_len bytes; host h's bytes
+ * are d_out[d_host_off[h] .. d_host_off[h + 1]), hosts in index order without
+ * gaps, a host that does not capture with an empty range.  d_host_off has
+ * n_hosts + 1 entries; d_out needs no alignment.  d_payload (payload_bytes
+ * bytes) may be NULL only when capture_len <= 28, the shortest header, so that
+ * no payload byte is reached; otherwise SRT_ERR_INVALID.
+ * Conditions, collected for srt_pcap_status; every write is range-checked first:
+ *   OVERFLOW      the call's bytes exceed out_cap: d_host_off is written in full
+ *                 (the caller sizes a retry), no byte of d_out is written, the
+ *                 hosts' last times and the counts do not advance;
+ *   BAD_PROTOCOL, BAD_LENGTH, BAD_PAYLOAD: the record is skipped, 0 bytes;
+ *   TIME_ORDER    a list decreases within a host, or a record is earlier than
+ *                 the last time this instance wrote for its host: the record is
+ *                 still written, in list order (its merge key is the largest
+ *                 time of its list so far).
+ * Asynchronous on the plan's stream, four launches: it never waits for the
+ * device and reads nothing back. */
+srt_status srt_pcap_run(srt_pcap *pc, const srt_pcap_rec *d_tx, const uint32_t *d_tx_idx,
+                        const uint32_t *d_tx_host_ptr, uint64_t n_tx, const srt_pcap_rec *d_rx,
+                        const uint32_t *d_rx_idx, const uint32_t *d_rx_host_ptr, uint64_t n_rx,
+                        const uint8_t *d_payload, uint64_t payload_bytes, uint8_t *d_out, uint64_t out_cap,
+                        uint64_t *d_host_off, srt_err *err);
+
+/* Synchronises the stream.  *flags (may be NULL): the SRT_PCAP_* conditions met
+ * since the last status call (then cleared); *n_records / *n_bytes (may be
+ * NULL): records and bytes written since create.  SRT_ERR_INVALID, with a
+ * message that names every flag set, when any was; else SRT_OK. */
+srt_status srt_pcap_status(srt_pcap *pc, uint32_t *flags, uint64_t *n_records, uint64_t *n_bytes, srt_err *err);
+
+/* The file side, host only.  srt_pcap_file_header: the 24 bytes a capture file
+ * starts with (pcap_writer.rs:25-54, native endian: magic 0xA1B2C3D4, version
+ * 2.4, thiszone 0, sigfigs 0, snaplen capture_len, linktype 101 LINKTYPE_RAW).
+ * srt_pcap_open_files: paths has n_hosts entries, NULL: no file for that host;
+ * each file is created or truncated, as File::create does, and gets the
+ * header; files open from an earlier call are closed first.
+ * srt_pcap_append_files: appends bytes[host_off[h] .. host_off[h + 1]) to host
+ * h's file, for a call's d_out and d_host_off copied to the host.  The files
+ * are closed by srt_pcap_destroy.  The reference names an interface's file
+ * <dir>/<hostname>-<interface name>.pcap (network_interface.c:403-414); the
+ * caller builds the paths. */
+void srt_pcap_file_header(uint32_t capture_len, uint8_t out[24]);
+srt_status srt_pcap_open_files(srt_pcap *pc, const char *const *paths, srt_err *err);
+srt_status srt_pcap_append_files(srt_pcap *pc, const uint64_t *host_off, const uint8_t *bytes, srt_err *err);
+
+/* the write pass's tile, in bytes: a workgroup assembles and stores that much of d_out at a time */
+uint32_t srt_pcap_tile_bytes(void);
+void srt_pcap_destroy(srt_pcap *pc);
 
 /* ---------------------------------------------------- IP assignment (a10) */
 /* IpAssignment<u32> (src/main/network/graph/mod.rs:352-420): IPv4 address ->

@@ -48,6 +48,9 @@ TRK_RETRANS = 1
 TRACKER_LOG_OVERRUN, TRACKER_NOTE_OVERRUN, TRACKER_BAD_SOCKET, TRACKER_BAD_HOST = 1, 2, 4, 8
 # srt_loopback_status flags
 LOOPBACK_TIME_ORDER, LOOPBACK_BAD_SOCKET, LOOPBACK_BAD_SLOT = 1, 2, 4
+# srt_pcap_create flags, srt_pcap_status flags
+PCAP_RX_FIRST, PCAP_TX_FIRST = 0, 1
+PCAP_OVERFLOW, PCAP_BAD_PROTOCOL, PCAP_BAD_LENGTH, PCAP_BAD_PAYLOAD, PCAP_TIME_ORDER = 1, 2, 4, 8, 16
 
 
 class SrtErr(C.Structure):
@@ -216,6 +219,15 @@ SIGNATURES = {
     "srt_loopback_tasks": (C.c_int, [_vp, _u64p, _errp]),
     "srt_loopback_status": (C.c_int, [_vp, _u32p, _u64p, _u64p, _errp]),
     "srt_loopback_destroy": (None, [_vp]),
+    "srt_pcap_create": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp), _errp]),
+    "srt_pcap_run": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp,
+                               C.c_uint64, _vp, _errp]),
+    "srt_pcap_status": (C.c_int, [_vp, _u32p, _u64p, _u64p, _errp]),
+    "srt_pcap_file_header": (None, [C.c_uint32, _vp]),
+    "srt_pcap_open_files": (C.c_int, [_vp, C.POINTER(C.c_char_p), _errp]),
+    "srt_pcap_append_files": (C.c_int, [_vp, _vp, _vp, _errp]),
+    "srt_pcap_tile_bytes": (C.c_uint32, []),
+    "srt_pcap_destroy": (None, [_vp]),
     "srt_routing_info_build": (C.c_int, [C.POINTER(SrtCsr), _u32p, C.c_uint32, C.c_int, C.POINTER(SrtOpts),
                                          C.POINTER(_vp), _errp]),
     "srt_routing_info_from_plan": (C.c_int, [_vp, C.POINTER(_vp), _errp]),

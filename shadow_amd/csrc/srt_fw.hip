@@ -3094,6 +3094,7 @@ hipError_t preload_flight();
 hipError_t preload_deliver();
 hipError_t preload_tracker();
 hipError_t preload_loopback();
+hipError_t preload_pcap();
 hipError_t preload_kernels() {
     hipError_t e = preload_fw();
     if (e == hipSuccess) e = preload_loss();
@@ -3109,6 +3110,7 @@ hipError_t preload_kernels() {
     if (e == hipSuccess) e = preload_deliver();
     if (e == hipSuccess) e = preload_tracker();
     if (e == hipSuccess) e = preload_loopback();
+    if (e == hipSuccess) e = preload_pcap();
     return e;
 }
 

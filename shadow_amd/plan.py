@@ -9,6 +9,7 @@ allocator here, every kernel is in libsrt.so.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional
 
 import numpy as np
@@ -932,6 +933,126 @@ class Tracker:
     def close(self):
         if self._h:
             _lib.lib().srt_tracker_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+PCAP_REC_DTYPE = np.dtype([("time_ns", "<u8"), ("payload_off", "<u8"), ("src_ip_be", "<u4"), ("dst_ip_be", "<u4"),
+                           ("src_port_be", "<u2"), ("dst_port_be", "<u2"), ("seq", "<u4"), ("ack", "<u4"),
+                           ("window", "<u2"), ("payload_len", "<u2"), ("protocol", "u1"), ("tcp_flags", "u1"),
+                           ("wscale", "u1"), ("wscale_set", "u1"), ("reserved", "<u4")])
+
+
+class PcapCapture:
+    """srt_pcap: the pcap capture of one interface class, a byte stream a
+    host, formatted where the pipeline runs: run() merges a span's sent and
+    received PCAP_REC_DTYPE records per host by time and writes every record
+    as 16 + incl_len bytes into `out`, host h's at out[host_off[h]:
+    host_off[h + 1]].  open_files() / append_files() are the file side, on
+    the host.
+
+    Bound to a RoutingPlan (arrays are torch CUDA tensors of its device, the
+    calls are asynchronous on its stream; closing the plan closes it), or
+    host-only with plan=None (arrays are numpy arrays, the same step on the
+    CPU)."""
+
+    def __init__(self, plan: Optional[RoutingPlan], n_hosts: int, capture_len: int, rec_cap: int, enabled=None,
+                 flags: int = _lib.PCAP_RX_FIRST):
+        self.plan = plan
+        self.n_hosts, self.capture_len, self.rec_cap = int(n_hosts), int(capture_len), int(rec_cap)
+        self._h = C.c_void_p()
+        en = None
+        if enabled is not None:
+            en = np.ascontiguousarray(np.asarray(enabled) != 0, np.uint8).reshape(-1)
+            if len(en) != self.n_hosts:
+                raise ValueError("PcapCapture: enabled has not n_hosts entries")
+        if plan is not None:
+            _bind_to_plan(self, plan)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_pcap_create(plan.handle if plan is not None else None, self.n_hosts,
+                                              self.capture_len, en.ctypes.data if en is not None and len(en) else None,
+                                              self.rec_cap, int(flags), C.byref(self._h), C.byref(err)), err)
+
+    _ptr = staticmethod(InboundRouter._ptr)
+    _nbytes = staticmethod(SendBatch._nbytes)
+    _streams = FlightStore._streams
+
+    def run(self, tx, tx_host_ptr, rx, rx_host_ptr, payload, out, host_off, tx_idx=None, rx_idx=None):
+        """srt_pcap_run.  tx / rx: uint8 views of 48-byte srt_pcap_rec records
+        (or None), tx_host_ptr / rx_host_ptr int32/uint32 [n_hosts+1], tx_idx /
+        rx_idx optional int32/uint32 indirections (the list's length is then
+        the index array's), payload uint8 or None, out uint8 (its size is
+        out_cap), host_off int64/uint64 [n_hosts+1].  Device form: enqueue
+        only; nothing is read back."""
+        n_tx = self._nbytes(tx_idx) // 4 if tx_idx is not None else self._nbytes(tx) // 48
+        n_rx = self._nbytes(rx_idx) // 4 if rx_idx is not None else self._nbytes(rx) // 48
+        if self._nbytes(tx_host_ptr) < 4 * (self.n_hosts + 1) or self._nbytes(rx_host_ptr) < 4 * (self.n_hosts + 1) or \
+                self._nbytes(host_off) < 8 * (self.n_hosts + 1):
+            raise ValueError("PcapCapture.run: an array is smaller than its record count")
+        cur, ps = self._streams(host_off)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_pcap_run(
+            self._h, self._ptr(tx) if n_tx else None, self._ptr(tx_idx), self._ptr(tx_host_ptr), n_tx,
+            self._ptr(rx) if n_rx else None, self._ptr(rx_idx), self._ptr(rx_host_ptr), n_rx,
+            self._ptr(payload) if self._nbytes(payload) else None, self._nbytes(payload),
+            self._ptr(out) if self._nbytes(out) else None, self._nbytes(out), self._ptr(host_off), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)
+
+    def status(self, check: bool = True):
+        """srt_pcap_status: synchronises; (flags, records written since create,
+        bytes written since create).  check=True raises SrtError when a flag
+        is set."""
+        flags, a, b = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        err = _lib.SrtErr()
+        rc = _lib.lib().srt_pcap_status(self._h, C.byref(flags), C.byref(a), C.byref(b), C.byref(err))
+        if check or (rc != _lib.SRT_OK and not flags.value):
+            _lib.check(rc, err)
+        return flags.value, a.value, b.value
+
+    @staticmethod
+    def file_header(capture_len: int) -> bytes:
+        """srt_pcap_file_header: the 24 bytes a capture file starts with."""
+        buf = C.create_string_buffer(24)
+        _lib.lib().srt_pcap_file_header(int(capture_len), C.cast(buf, C.c_void_p))
+        return buf.raw
+
+    @staticmethod
+    def tile_bytes() -> int:
+        """srt_pcap_tile_bytes: the write pass's tile."""
+        return int(_lib.lib().srt_pcap_tile_bytes())
+
+    def open_files(self, paths):
+        """srt_pcap_open_files: paths, n_hosts file names (None: no file);
+        each is created or truncated and gets the file header.  The
+        reference's name is <dir>/<hostname>-<interface name>.pcap."""
+        if len(paths) != self.n_hosts:
+            raise ValueError("PcapCapture.open_files: paths has not n_hosts entries")
+        arr = (C.c_char_p * max(1, self.n_hosts))(*[None if p is None else os.fsencode(p) for p in paths])
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_pcap_open_files(self._h, arr, C.byref(err)), err)
+
+    def append_files(self, host_off, data):
+        """srt_pcap_append_files: a call's host_off and out bytes, on the host
+        (numpy arrays), appended to the hosts' files."""
+        ho = np.ascontiguousarray(host_off).view(np.uint64).reshape(-1)
+        if len(ho) != self.n_hosts + 1:
+            raise ValueError("PcapCapture.append_files: host_off has not n_hosts + 1 entries")
+        d = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        if len(d) < int(ho[-1]):
+            raise ValueError("PcapCapture.append_files: data is shorter than host_off[n_hosts]")
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_pcap_append_files(self._h, ho.ctypes.data, d.ctypes.data if len(d) else None,
+                                                    C.byref(err)), err)
+
+    def close(self):
+        if self._h:
+            _lib.lib().srt_pcap_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
