@@ -56,6 +56,7 @@
 
 #include "srt_internal.h"
 #include "srt_deliver_step.h"
+#include "srt_stage.h"
 
 namespace {
 
@@ -63,11 +64,9 @@ static_assert(sizeof(srt_rx_meta) == 16 && sizeof(srt_assoc) == 20 && sizeof(del
                   sizeof(deliver::LogRec) == 32 && sizeof(deliver::State) == 24 && sizeof(srt_inbound_late) == 24,
               "record layouts");
 
-constexpr uint32_t BT = 256;            // threads a workgroup of (1), (2), (4) and the note
-constexpr uint32_t ST = 1024;           // threads of the scan's one workgroup
-constexpr uint32_t LATE_BLOCKS = 1024;  // at most, each striding over the late list
-constexpr uint32_t NOTE_BLOCKS = 4096;  // at most, each striding over the note
-constexpr uint32_t WIDE_AVG = 16;       // more packets a host on average: a wave a host
+using stage::BT;
+using stage::ST;
+using stage::set_err;
 constexpr uint32_t DL_CAP = deliver::SORT_CAP;
 constexpr uint32_t ORDER_BLOCKS = 1u << 20;  // at most, each striding over the hosts
 
@@ -79,73 +78,54 @@ __global__ __launch_bounds__(BT) void deliver_note_kernel(const deliver::Ctx c) 
 
 template <uint32_t L>
 __global__ __launch_bounds__(BT) void deliver_count_kernel(const deliver::Ctx c) {
-    const uint64_t g = ((uint64_t)blockIdx.x * BT + threadIdx.x) / L;
-    const uint32_t l = threadIdx.x % L;
+    const stage::Group<L> G(c.n_hosts);
     uint32_t n = 0;
-    if (g < c.n_hosts) {
+    if (G.own()) {
         const uint32_t lim = deliver::walked(c);
         uint32_t b, e;
-        deliver::segment(c, lim, (uint32_t)g, b, e);
-        for (uint32_t i = b + l; i < e; i += L) {
+        deliver::segment(c, lim, (uint32_t)G.g, b, e);
+        for (uint32_t i = b + G.l; i < e; i += L) {
             const uint32_t st = c.status[i];
             if (deliver::forwarded(st)) ++n;
             else deliver::log_keep(c, lim, i, st);
         }
     }
-    // every lane is here: the group's lanes hold its partial counts
+    // every lane is here: the group's lanes hold its partial counts (written out: through stage::group_add
+    // the three stores below are scheduled in another order)
     for (uint32_t off = L / 2; off > 0; off >>= 1) n += __shfl_xor(n, off);
-    if (g < c.n_hosts && l == 0) {
-        c.cnt[g] = n;
-        c.nlate[g] = 0;
-        c.lfill[g] = 0;
+    if (G.own() && G.l == 0) {
+        c.cnt[G.g] = n;
+        c.nlate[G.g] = 0;
+        c.lfill[G.g] = 0;
     }
 }
 
 __global__ __launch_bounds__(BT) void deliver_late_kernel(const deliver::Ctx c) {
-    const uint32_t n = deliver::late_n(c);
-    for (uint64_t k = (uint64_t)blockIdx.x * BT + threadIdx.x; k < n; k += (uint64_t)gridDim.x * BT)
-        deliver::count_late(c, (uint32_t)k);
+    for (uint64_t k : stage::grid_stride(deliver::late_n(c))) deliver::count_late(c, (uint32_t)k);
 }
 
 __global__ __launch_bounds__(ST) void deliver_scan_kernel(const deliver::Ctx c) {
-    __shared__ uint64_t wsum[ST / 64];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (uint32_t)(((uint64_t)c.n_hosts + ST - 1) / ST);  // below 2^22: t * per fits
-    const uint64_t b64 = (uint64_t)t * per;
-    const uint32_t b = b64 < c.n_hosts ? (uint32_t)b64 : c.n_hosts;
-    const uint32_t e = b64 + per < c.n_hosts ? (uint32_t)(b64 + per) : c.n_hosts;
-    uint64_t sum = 0;
-    for (uint32_t h = b; h < e; ++h) sum += (uint64_t)c.cnt[h] + c.nlate[h];
-    // inclusive scan of the threads' sums: within the wave, then over the waves' totals
-    uint64_t inc = sum;
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-        const unsigned long long o = __shfl_up((unsigned long long)inc, off);
-        if ((t & 63) >= off) inc += o;
-    }
-    if ((t & 63) == 63) wsum[t >> 6] = inc;
-    __syncthreads();
-    uint64_t before = 0;
-    for (uint32_t w = 0; w < (t >> 6); ++w) before += wsum[w];
-    uint64_t run = before + inc - sum;
-    for (uint32_t h = b; h < e; ++h) {
-        c.out_host_ptr[h] = deliver::host_base(c, run);
-        run += (uint64_t)c.cnt[h] + c.nlate[h];
-    }
-    if (t == ST - 1) deliver::scan_end(c, before + inc);
+    stage::scan_hosts<ST>(
+        c.n_hosts, [&](uint32_t h) { return (uint64_t)c.cnt[h] + c.nlate[h]; },
+        [&](uint32_t h, uint64_t run) {
+            c.out_host_ptr[h] = deliver::host_base(c, run);
+            return (uint64_t)c.cnt[h] + c.nlate[h];
+        },
+        [&](uint64_t total) { deliver::scan_end(c, total); });
 }
 
 template <uint32_t L>
 __global__ __launch_bounds__(BT) void deliver_scatter_kernel(const deliver::Ctx c, uint32_t host_blocks) {
     if (blockIdx.x < host_blocks) {
-        const uint64_t g = ((uint64_t)blockIdx.x * BT + threadIdx.x) / L;
-        const uint32_t l = threadIdx.x % L, lane = threadIdx.x & 63;
+        const stage::Group<L> G(c.n_hosts);
+        const uint32_t l = G.l, lane = threadIdx.x & 63;
         const uint32_t shift = lane & ~(L - 1);  // the group's first lane in the wave's ballot
         uint64_t gmask = ~0ull;
         if constexpr (L < 64) gmask = ((1ull << L) - 1ull) << shift;
         uint32_t b = 0, e = 0, h = 0;
         uint64_t pos = 0;
-        if (g < c.n_hosts) {
-            h = (uint32_t)g;
+        if (G.own()) {
+            h = (uint32_t)G.g;
             deliver::segment(c, deliver::walked(c), h, b, e);
             pos = (uint64_t)c.out_host_ptr[h] + c.nlate[h];
         }
@@ -157,8 +137,8 @@ __global__ __launch_bounds__(BT) void deliver_scatter_kernel(const deliver::Ctx 
             if (fw) miss += deliver::emit_batch(c, h, i, pos + (uint64_t)__popcll(m & ((1ull << lane) - 1ull)));
             pos += (uint64_t)__popcll(m);
         }
-        for (uint32_t off = L / 2; off > 0; off >>= 1) miss += __shfl_xor(miss, off);
-        if (g < c.n_hosts && l == 0) c.cnt[h] = miss;  // the batch count has been scanned: the word is free
+        for (uint32_t off = L / 2; off > 0; off >>= 1) miss += __shfl_xor(miss, off);  // written out, as in the count
+        if (G.own() && l == 0) c.cnt[h] = miss;  // the batch count has been scanned: the word is free
     } else {
         const uint32_t n = deliver::late_n(c);
         const uint64_t stride = (uint64_t)(gridDim.x - host_blocks) * BT;
@@ -198,7 +178,7 @@ __global__ __launch_bounds__(64) void deliver_order_kernel(const deliver::Ctx c)
         __syncthreads();  // every rank of the run is written
         uint32_t miss = 0;
         for (uint32_t j = t; j < m; j += 64) miss += deliver::emit_late(c, h, b + j, c.out_socket[b + j], n_late);
-        for (uint32_t off = 32; off > 0; off >>= 1) miss += __shfl_xor(miss, off);
+        miss = stage::group_add<64>(miss);
         if (t == 0) c.cnt[h] += miss;  // this workgroup alone has host h now
         __syncthreads();  // LDS reused by the next host
     }
@@ -229,12 +209,6 @@ __global__ __launch_bounds__(BT) void deliver_lookup_kernel(const deliver::Slot 
     if (k >= n) return;
     const uint32_t h = hosts[k];
     sockets[k] = h < n_hosts ? deliver::lookup(table, mask, h, meta[k]) : deliver::NO_SOCKET;
-}
-
-void set_err(srt_err *err, srt_status code, const char *msg) {
-    if (!err) return;
-    err->code = code;
-    std::snprintf(err->msg, sizeof err->msg, "%s", msg);
 }
 
 // (host, protocol, local port, peer ip, peer port)
@@ -333,7 +307,7 @@ srt_status deliver_table(srt_deliver *dl, srt_plan **plan, uint32_t *n_hosts, co
                          uint32_t *mask, srt_err *err) {
     *plan = dl->plan;
     *n_hosts = dl->n_hosts;
-    if (dl->plan && hipSetDevice(dl->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    if (dl->plan && !stage::use_device(dl->plan)) return SRT_ERR_HIP;
     const srt_status up = upload(dl, err);
     if (up != SRT_OK) return up;
     *table = dl->plan ? dl->d_table : dl->h_table.data();
@@ -345,7 +319,7 @@ srt_status deliver_table(srt_deliver *dl, srt_plan **plan, uint32_t *n_hosts, co
 extern "C" void srt_deliver_destroy(srt_deliver *dl) {
     if (!dl) return;
     if (dl->plan) {
-        (void)hipSetDevice(dl->plan->device);
+        (void)stage::use_device(dl->plan);
         (void)hipStreamSynchronize(dl->plan->stream);
         (void)hipFree(dl->mem);
         (void)hipFree(dl->d_table);
@@ -357,11 +331,8 @@ extern "C" void srt_deliver_destroy(srt_deliver *dl) {
 
 extern "C" srt_status srt_deliver_create(srt_plan *plan, uint32_t n_hosts, uint32_t table_slots_min, uint64_t note_cap,
                                          uint64_t log_cap, srt_deliver **out, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!out) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!out) return stage::null_argument(err);
     *out = nullptr;
     if (n_hosts == 0xffffffffu || table_slots_min > (1u << 30) || note_cap > (1ull << 31) || log_cap > (1ull << 31)) {
         set_err(err, SRT_ERR_INVALID,
@@ -388,7 +359,7 @@ extern "C" srt_status srt_deliver_create(srt_plan *plan, uint32_t n_hosts, uint3
         dl->mem = dl->h_mem.data();
     } else if (ok) {
         srt::init_wait();
-        ok = hipSetDevice(plan->device) == hipSuccess;
+        ok = stage::use_device(plan);
         ok = ok && hipMalloc(&dl->mem, bytes + 8) == hipSuccess;
         ok = ok && hipMemset(dl->mem, 0, bytes + 8) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&dl->up_done, hipEventDisableTiming) == hipSuccess;
@@ -420,11 +391,8 @@ extern "C" srt_status srt_deliver_create(srt_plan *plan, uint32_t n_hosts, uint3
 }
 
 extern "C" srt_status srt_deliver_associate(srt_deliver *dl, const srt_assoc *assoc, uint64_t n, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!dl || (n && !assoc)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!dl || (n && !assoc)) return stage::null_argument(err);
     try {
         // nothing changes unless the whole batch can go in
         std::vector<Key> keys;
@@ -456,11 +424,8 @@ extern "C" srt_status srt_deliver_associate(srt_deliver *dl, const srt_assoc *as
 }
 
 extern "C" srt_status srt_deliver_disassociate(srt_deliver *dl, const srt_assoc *assoc, uint64_t n, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!dl || (n && !assoc)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!dl || (n && !assoc)) return stage::null_argument(err);
     for (uint64_t k = 0; k < n; ++k)
         if (dl->assoc.erase(key_of(assoc[k]))) dl->stale = true;
     return SRT_OK;
@@ -468,11 +433,8 @@ extern "C" srt_status srt_deliver_disassociate(srt_deliver *dl, const srt_assoc 
 
 extern "C" srt_status srt_deliver_lookup(srt_deliver *dl, const uint32_t *hosts, const srt_rx_meta *meta, uint64_t n,
                                          uint32_t *sockets, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!dl || (n && (!hosts || !meta || !sockets))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!dl || (n && (!hosts || !meta || !sockets))) return stage::null_argument(err);
     if (!rebuild(dl)) {
         set_err(err, SRT_ERR_OOM, "deliver: host allocation failed");
         return SRT_ERR_OOM;
@@ -484,34 +446,24 @@ extern "C" srt_status srt_deliver_lookup(srt_deliver *dl, const uint32_t *hosts,
 extern "C" srt_status srt_deliver_lookup_flat(srt_deliver *dl, const uint32_t *d_hosts, const srt_rx_meta *d_meta,
                                               uint64_t n, uint32_t *d_sockets, srt_err *err) {
     if (!dl || !dl->plan) return srt_deliver_lookup(dl, d_hosts, d_meta, n, d_sockets, err);
-    if (err) std::memset(err, 0, sizeof *err);
-    if (n && (!d_hosts || !d_meta || !d_sockets)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (n && (!d_hosts || !d_meta || !d_sockets)) return stage::null_argument(err);
     if (n >= 0x80000000ull) {
         set_err(err, SRT_ERR_INVALID, "more than 2^31-1 records in one call");
         return SRT_ERR_INVALID;
     }
-    if (hipSetDevice(dl->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    if (!stage::use_device(dl->plan)) return SRT_ERR_HIP;
     const srt_status up = upload(dl, err);
     if (up != SRT_OK || !n) return up;
     hipLaunchKernelGGL(deliver_lookup_kernel, dim3((uint32_t)((n + BT - 1) / BT)), dim3(BT), 0, dl->plan->stream,
                        dl->d_table, dl->slots - 1, dl->n_hosts, d_hosts, d_meta, (uint32_t)n, d_sockets);
-    if (hipGetLastError() != hipSuccess) {
-        set_err(err, SRT_ERR_HIP, "deliver: launch failed");
-        return SRT_ERR_HIP;
-    }
-    return SRT_OK;
+    return stage::launched(err, "deliver");
 }
 
 extern "C" srt_status srt_deliver_table_stats(srt_deliver *dl, uint64_t *n_assoc, uint32_t *n_slots,
                                               uint32_t *max_probe, uint32_t *wrapped, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!dl) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!dl) return stage::null_argument(err);
     if (!rebuild(dl)) {
         set_err(err, SRT_ERR_OOM, "deliver: host allocation failed");
         return SRT_ERR_OOM;
@@ -525,11 +477,8 @@ extern "C" srt_status srt_deliver_table_stats(srt_deliver *dl, uint64_t *n_assoc
 
 extern "C" srt_status srt_deliver_note(srt_deliver *dl, const srt_rx_meta *d_meta, uint64_t n_pkts, uint64_t tag_base,
                                        srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!dl || (n_pkts && !d_meta)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!dl || (n_pkts && !d_meta)) return stage::null_argument(err);
     if (n_pkts >= 0x80000000ull || tag_base < dl->note_end || tag_base + n_pkts < tag_base) {
         set_err(err, SRT_ERR_INVALID, "deliver: more than 2^31-1 packets in one note, or tag_base below the previous note's end");
         return SRT_ERR_INVALID;
@@ -545,14 +494,10 @@ extern "C" srt_status srt_deliver_note(srt_deliver *dl, const srt_rx_meta *d_met
         deliver::host_note(c);
         return SRT_OK;
     }
-    if (hipSetDevice(dl->plan->device) != hipSuccess) return SRT_ERR_HIP;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_pkts - c.note_first + BT - 1) / BT, NOTE_BLOCKS);
-    hipLaunchKernelGGL(deliver_note_kernel, dim3(blocks), dim3(BT), 0, dl->plan->stream, c);
-    if (hipGetLastError() != hipSuccess) {
-        set_err(err, SRT_ERR_HIP, "deliver: launch failed");
-        return SRT_ERR_HIP;
-    }
-    return SRT_OK;
+    if (!stage::use_device(dl->plan)) return SRT_ERR_HIP;
+    hipLaunchKernelGGL(deliver_note_kernel, dim3(stage::strided_blocks(n_pkts - c.note_first, stage::NOTE_BLOCKS)),
+                       dim3(BT), 0, dl->plan->stream, c);
+    return stage::launched(err, "deliver");
 }
 
 extern "C" srt_status srt_deliver_run(srt_deliver *dl, const uint32_t *d_dst_ptr, uint64_t n_pkts,
@@ -561,18 +506,16 @@ extern "C" srt_status srt_deliver_run(srt_deliver *dl, const uint32_t *d_dst_ptr
                                       const uint32_t *d_late_count, uint32_t *d_out_host_ptr, uint32_t *d_out_socket,
                                       uint64_t *d_out_forward_ns, uint64_t *d_out_tag, uint32_t *d_out_user,
                                       uint32_t *d_out_status, uint64_t out_cap, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
+    stage::begin(err);
     if (!dl || !d_dst_ptr || !d_out_host_ptr || (n_pkts && (!d_tag || !d_status || !d_forward_ns)) ||
         (late_cap && (!d_late || !d_late_count)) ||
-        (out_cap && (!d_out_socket || !d_out_forward_ns || !d_out_tag || !d_out_user || !d_out_status))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+        (out_cap && (!d_out_socket || !d_out_forward_ns || !d_out_tag || !d_out_user || !d_out_status)))
+        return stage::null_argument(err);
     if (n_pkts >= 0x80000000ull || late_cap >= 0x80000000u) {
         set_err(err, SRT_ERR_INVALID, "more than 2^31-1 packets in one batch or late list");
         return SRT_ERR_INVALID;
     }
-    if (dl->plan && hipSetDevice(dl->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    if (dl->plan && !stage::use_device(dl->plan)) return SRT_ERR_HIP;
     const srt_status up = upload(dl, err);
     if (up != SRT_OK) return up;
     deliver::Ctx c = dl->base;
@@ -609,54 +552,36 @@ extern "C" srt_status srt_deliver_run(srt_deliver *dl, const uint32_t *d_dst_ptr
     }
     hipStream_t s = dl->plan->stream;
     dl->ran = true;
-    const bool wide = n_pkts > (uint64_t)WIDE_AVG * c.n_hosts;
-    const uint32_t per_block = wide ? BT / 64 : BT / 8;
-    const uint32_t host_blocks = (uint32_t)(((uint64_t)c.n_hosts + per_block - 1) / per_block);
-    const uint32_t late_blocks = late_cap ? std::min<uint32_t>((late_cap + BT - 1) / BT, LATE_BLOCKS) : 0;
-    if (host_blocks) {
-        if (wide) hipLaunchKernelGGL(deliver_count_kernel<64>, dim3(host_blocks), dim3(BT), 0, s, c);
-        else hipLaunchKernelGGL(deliver_count_kernel<8>, dim3(host_blocks), dim3(BT), 0, s, c);
-    }
+    const bool wide = stage::wide(n_pkts, c.n_hosts);
+    const uint32_t host_blocks = stage::host_blocks(c.n_hosts, wide);
+    const uint32_t late_blocks = stage::strided_blocks(late_cap, stage::LATE_BLOCKS);
+    if (host_blocks)
+        stage::launch_grouped(deliver_count_kernel<64>, deliver_count_kernel<8>, wide, host_blocks, BT, s, c);
     if (late_blocks) hipLaunchKernelGGL(deliver_late_kernel, dim3(late_blocks), dim3(BT), 0, s, c);
     hipLaunchKernelGGL(deliver_scan_kernel, dim3(1), dim3(ST), 0, s, c);
     if (host_blocks) {
-        if (wide)
-            hipLaunchKernelGGL(deliver_scatter_kernel<64>, dim3(host_blocks + late_blocks), dim3(BT), 0, s, c,
-                               host_blocks);
-        else
-            hipLaunchKernelGGL(deliver_scatter_kernel<8>, dim3(host_blocks + late_blocks), dim3(BT), 0, s, c,
-                               host_blocks);
+        stage::launch_grouped(deliver_scatter_kernel<64>, deliver_scatter_kernel<8>, wide,
+                              host_blocks + late_blocks, BT, s, c, host_blocks);
         if (late_blocks)
             hipLaunchKernelGGL(deliver_order_kernel, dim3(std::min(c.n_hosts, ORDER_BLOCKS)), dim3(64), 0, s, c);
     }
-    if (hipGetLastError() != hipSuccess) {
-        set_err(err, SRT_ERR_HIP, "deliver: launch failed");
-        return SRT_ERR_HIP;
-    }
-    return SRT_OK;
+    return stage::launched(err, "deliver");
 }
 
 extern "C" srt_status srt_deliver_status(srt_deliver *dl, uint32_t *flags, uint64_t *n_delivered,
                                          uint64_t *n_no_socket, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!dl) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!dl) return stage::null_argument(err);
     deliver::State w;
     if (!dl->plan) {
         w = *dl->base.st;
         dl->base.st->flags = 0;
     } else {
-        if (hipSetDevice(dl->plan->device) != hipSuccess) return SRT_ERR_HIP;
-        hipStream_t s = dl->plan->stream;
-        if (dl->ran && dl->n_hosts) hipLaunchKernelGGL(deliver_sum_kernel, dim3(1), dim3(ST), 0, s, dl->base);
-        if (hipMemcpyAsync(&w, dl->base.st, sizeof w, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            set_err(err, SRT_ERR_HIP, "deliver: stream failed");
-            return SRT_ERR_HIP;
-        }
-        if (w.flags) (void)hipMemsetAsync(&dl->base.st->flags, 0, 4, s);
+        if (!stage::use_device(dl->plan)) return SRT_ERR_HIP;
+        if (dl->ran && dl->n_hosts)
+            hipLaunchKernelGGL(deliver_sum_kernel, dim3(1), dim3(ST), 0, dl->plan->stream, dl->base);
+        const srt_status st = stage::read_status(dl->plan, &w, dl->base.st, sizeof w, err, "deliver");
+        if (st != SRT_OK) return st;
     }
     const uint32_t f = w.flags & 15u;
     if (flags) *flags = f;

@@ -167,23 +167,16 @@ SRT_HD bool note_read(const Ctx &c, uint64_t tag, srt_rx_meta &m) {
 }
 
 // ---- the walk
-SRT_HD uint32_t walked(const Ctx &c) { return c.dst_ptr[c.n_hosts] < c.n_pkts ? c.dst_ptr[c.n_hosts] : c.n_pkts; }
+SRT_HD uint32_t walked(const Ctx &c) { return relay::walked(c.dst_ptr, c.n_hosts, c.n_pkts); }
 
-// host h's segment of the window, held inside it whatever dst_ptr[] says
+// host h's segment of the window of `lim` walked packets
 SRT_HD void segment(const Ctx &c, uint32_t lim, uint32_t h, uint32_t &b, uint32_t &e) {
-    b = c.dst_ptr[h] < lim ? c.dst_ptr[h] : lim;
-    e = c.dst_ptr[h + 1] < lim ? c.dst_ptr[h + 1] : lim;
-    if (e < b) e = b;
+    relay::segment(c.dst_ptr, lim, h, b, e);
 }
 
 SRT_HD bool forwarded(uint32_t status) { return (status & SRT_PDS_RELAY_FORWARDED) != 0; }
 
-// records of the late list that exist: the count runs past the cap on overflow
-SRT_HD uint32_t late_n(const Ctx &c) {
-    if (!c.late_count) return 0;
-    const uint32_t n = *c.late_count;
-    return n < c.late_cap ? n : c.late_cap;
-}
+SRT_HD uint32_t late_n(const Ctx &c) { return relay::late_n(c.late_count, c.late_cap); }
 
 // batch packet i of a window of `lim` walked packets is not forwarded: if it stays in the stage
 // (enqueued, neither forwarded nor dropped) its tag and meta go to the log
@@ -217,7 +210,7 @@ SRT_HD void count_late(const Ctx &c, uint32_t k) {
 }
 
 // the scan's output for a host whose packets begin at `prefix`
-SRT_HD uint32_t host_base(const Ctx &c, uint64_t prefix) { return (uint32_t)(prefix < c.out_cap ? prefix : c.out_cap); }
+SRT_HD uint32_t host_base(const Ctx &c, uint64_t prefix) { return relay::host_base(prefix, c.out_cap); }
 
 SRT_HD void scan_end(const Ctx &c, uint64_t total) {
     c.out_host_ptr[c.n_hosts] = host_base(c, total);

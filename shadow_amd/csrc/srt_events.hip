@@ -29,8 +29,11 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "srt_internal.h"
+#include "srt_stage.h"
 
 namespace {
+
+using stage::set_err;
 
 constexpr uint32_t EV_CAP = 1024;  // events a destination group may hold for the LDS sort
 
@@ -329,12 +332,6 @@ __global__ void event_dst_ptr_kernel(const uint32_t *__restrict__ kdst, uint64_t
         else hi = mid;
     }
     dst_ptr[d] = (uint32_t)lo;
-}
-
-void set_err(srt_err *err, srt_status code, const char *msg) {
-    if (!err) return;
-    err->code = code;
-    std::snprintf(err->msg, sizeof err->msg, "%s", msg);
 }
 
 int bit_width(uint32_t x) {

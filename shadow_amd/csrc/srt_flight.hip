@@ -44,17 +44,18 @@
 
 #include "srt_internal.h"
 #include "srt_flight_step.h"
+#include "srt_stage.h"
 
 namespace {
 
 static_assert(sizeof(flight::State) == 48 && sizeof(flight::Rec) == 32, "state and record layouts");
 
-constexpr uint32_t BT = 256;         // threads a workgroup of (1) and (3)
+using stage::BT;  // threads a workgroup of (1) and (3)
+using stage::ST;
+using stage::set_err;
 constexpr uint32_t PT = 1024;        // threads a workgroup of the push: one atomic for 16 or 128 hosts
-constexpr uint32_t ST = 1024;        // threads of the scan's one workgroup
 constexpr uint32_t ITEMS = 4;        // records a thread of (3) moves a step: 1,024 a workgroup
 constexpr uint32_t MAX_BLOCKS = 2048;  // of the grid-stride launches
-constexpr uint32_t WIDE_AVG = 16;    // more packets a host on average: a wave a host
 constexpr uint32_t FL_CAP = 256;     // G: the records a destination's run may hold for the one-pass LDS sort
 constexpr uint32_t SORT_BLOCKS = 1u << 20;  // at most, each striding over the destinations
 
@@ -62,10 +63,10 @@ template <uint32_t L>
 __global__ __launch_bounds__(PT) void flight_push_kernel(const flight::Ctx c) {
     __shared__ uint32_t wtot[PT / 64];
     __shared__ unsigned long long bbase;
-    const uint64_t g = ((uint64_t)blockIdx.x * PT + threadIdx.x) / L;
-    const uint32_t l = threadIdx.x % L, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const stage::Group<L, PT> G(c.n_src);
+    const uint32_t l = G.l, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t b = 0, e = 0;
-    if (g < c.n_src) flight::segment(c, (uint32_t)g, b, e);
+    if (G.own()) flight::segment(c, (uint32_t)G.g, b, e);
     const flight::Pool to = flight::half(c, c.st->cur);
     // every lane of the wave takes every step: the ballots are over the whole wave
     uint32_t wcount = 0;
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(PT) void flight_push_kernel(const flight::Ctx c) {
         const bool take = i < e && flight::push_takes(c, i);
         const uint64_t m = __ballot(take);
         const bool lost = take && !flight::push_store(c, to, place + (uint64_t)__popcll(m & ((1ull << lane) - 1ull)),
-                                                      (uint32_t)g, i);
+                                                      (uint32_t)G.g, i);
         place += (uint64_t)__popcll(m);
         const uint64_t lm = __ballot(lost);
         if (lane == 0) flight::push_lost(c, (uint64_t)__popcll(lm));
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(PT) void flight_push_kernel(const flight::Ctx c) {
 __global__ __launch_bounds__(BT) void flight_count_kernel(const flight::Ctx c) {
     const flight::Pool from = flight::half(c, c.st->cur);
     const uint64_t n = flight::stored(c, c.st->len);
-    for (uint64_t i = (uint64_t)blockIdx.x * BT + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BT)
+    for (uint64_t i : stage::grid_stride(n))
         if (flight::due(c, from, i)) flight::count_due(c, from, i);
 }
 
@@ -265,12 +266,6 @@ __global__ __launch_bounds__(64) void flight_sort_kernel(const flight::Ctx c) {
     }
 }
 
-void set_err(srt_err *err, srt_status code, const char *msg) {
-    if (!err) return;
-    err->code = code;
-    std::snprintf(err->msg, sizeof err->msg, "%s", msg);
-}
-
 }  // namespace
 
 struct srt_flight {
@@ -296,7 +291,7 @@ hipError_t preload_flight() {
 extern "C" void srt_flight_destroy(srt_flight *fl) {
     if (!fl) return;
     if (fl->plan) {
-        (void)hipSetDevice(fl->plan->device);
+        (void)stage::use_device(fl->plan);
         (void)hipStreamSynchronize(fl->plan->stream);
         (void)hipFree(fl->mem);
     }
@@ -305,11 +300,8 @@ extern "C" void srt_flight_destroy(srt_flight *fl) {
 
 extern "C" srt_status srt_flight_create(srt_plan *plan, uint32_t n_dst_hosts, uint64_t pool_cap, srt_flight **out,
                                         srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!out) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!out) return stage::null_argument(err);
     *out = nullptr;
     if (n_dst_hosts == 0xffffffffu || pool_cap > (1ull << 31)) {
         set_err(err, SRT_ERR_INVALID, "flight: n_dst_hosts or pool_cap (at most 2^31) out of range");
@@ -334,7 +326,7 @@ extern "C" srt_status srt_flight_create(srt_plan *plan, uint32_t n_dst_hosts, ui
         fl->mem = fl->h_mem.data();
     } else {
         srt::init_wait();
-        bool ok = hipSetDevice(plan->device) == hipSuccess;
+        bool ok = stage::use_device(plan);
         ok = ok && hipMalloc(&fl->mem, bytes + 8) == hipSuccess;
         ok = ok && hipMemset(fl->mem, 0, head) == hipSuccess;
         if (!ok) {
@@ -371,12 +363,10 @@ extern "C" srt_status srt_flight_push(srt_flight *fl, const uint32_t *d_host_pkt
                                       const uint32_t *d_dst_host, const uint64_t *d_event_id,
                                       const uint32_t *d_total_size, const uint64_t *d_tag, uint64_t *tag_base,
                                       srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
+    stage::begin(err);
     if (!fl || !d_host_pkt_ptr ||
-        (n_pkts && (!d_flags || !d_deliver || !d_dst_host || !d_event_id || !d_total_size))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+        (n_pkts && (!d_flags || !d_deliver || !d_dst_host || !d_event_id || !d_total_size)))
+        return stage::null_argument(err);
     if (n_pkts >= 0x80000000ull || n_src_hosts == 0xffffffffu) {
         set_err(err, SRT_ERR_INVALID, "more than 2^31-1 packets in one batch, or n_src_hosts out of range");
         return SRT_ERR_INVALID;
@@ -401,28 +391,20 @@ extern "C" srt_status srt_flight_push(srt_flight *fl, const uint32_t *d_host_pkt
         return SRT_OK;
     }
     if (!n_pkts || !n_src_hosts) return SRT_OK;
-    if (hipSetDevice(fl->plan->device) != hipSuccess) return SRT_ERR_HIP;
-    const bool wide = n_pkts > (uint64_t)WIDE_AVG * c.n_src;
-    const uint32_t per_block = wide ? PT / 64 : PT / 8;
-    const uint32_t blocks = (uint32_t)(((uint64_t)c.n_src + per_block - 1) / per_block);
-    if (wide) hipLaunchKernelGGL(flight_push_kernel<64>, dim3(blocks), dim3(PT), 0, fl->plan->stream, c);
-    else hipLaunchKernelGGL(flight_push_kernel<8>, dim3(blocks), dim3(PT), 0, fl->plan->stream, c);
-    if (hipGetLastError() != hipSuccess) {
-        set_err(err, SRT_ERR_HIP, "flight: launch failed");
-        return SRT_ERR_HIP;
-    }
-    return SRT_OK;
+    if (!stage::use_device(fl->plan)) return SRT_ERR_HIP;
+    const bool wide = stage::wide(n_pkts, c.n_src);
+    stage::launch_grouped(flight_push_kernel<64>, flight_push_kernel<8>, wide,
+                          stage::host_blocks(c.n_src, wide, PT), PT, fl->plan->stream, c);
+    return stage::launched(err, "flight");
 }
 
 extern "C" srt_status srt_flight_pop(srt_flight *fl, uint64_t until_ns, uint32_t *d_w_order, uint32_t *d_w_dst_ptr,
                                      uint64_t *d_w_deliver, uint32_t *d_w_total_size, uint32_t *d_w_src_host,
                                      uint64_t *d_w_event_id, uint64_t *d_w_tag, uint64_t out_cap, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
+    stage::begin(err);
     if (!fl || !d_w_dst_ptr ||
-        (out_cap && (!d_w_order || !d_w_deliver || !d_w_total_size || !d_w_src_host || !d_w_event_id || !d_w_tag))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+        (out_cap && (!d_w_order || !d_w_deliver || !d_w_total_size || !d_w_src_host || !d_w_event_id || !d_w_tag)))
+        return stage::null_argument(err);
     flight::Ctx c = fl->base;
     c.until = until_ns;
     c.out_cap = out_cap < 0xffffffffull ? out_cap : 0xffffffffull;  // positions are u32
@@ -440,42 +422,30 @@ extern "C" srt_status srt_flight_pop(srt_flight *fl, uint64_t until_ns, uint32_t
         flight::host_pop(c);
         return SRT_OK;
     }
-    if (hipSetDevice(fl->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    if (!stage::use_device(fl->plan)) return SRT_ERR_HIP;
     hipStream_t s = fl->plan->stream;
-    const uint32_t count_blocks = (uint32_t)std::min<uint64_t>((fl->bound + BT - 1) / BT, MAX_BLOCKS);
+    const uint32_t count_blocks = stage::strided_blocks(fl->bound, MAX_BLOCKS);
     const uint32_t move_blocks = (uint32_t)std::min<uint64_t>((fl->bound + BT * ITEMS - 1) / (BT * ITEMS), MAX_BLOCKS);
     if (count_blocks) hipLaunchKernelGGL(flight_count_kernel, dim3(count_blocks), dim3(BT), 0, s, c);
     hipLaunchKernelGGL(flight_scan_kernel, dim3(1), dim3(ST), 0, s, c);
     if (move_blocks) hipLaunchKernelGGL(flight_move_kernel, dim3(move_blocks), dim3(BT), 0, s, c);
     if (move_blocks && c.n_dst)
         hipLaunchKernelGGL(flight_sort_kernel, dim3(std::min(c.n_dst, SORT_BLOCKS)), dim3(64), 0, s, c);
-    if (hipGetLastError() != hipSuccess) {
-        set_err(err, SRT_ERR_HIP, "flight: launch failed");
-        return SRT_ERR_HIP;
-    }
-    return SRT_OK;
+    return stage::launched(err, "flight");
 }
 
 extern "C" srt_status srt_flight_status(srt_flight *fl, uint32_t *flags, uint64_t *n_popped, uint64_t *n_stored,
                                         uint64_t *n_lost, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!fl) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!fl) return stage::null_argument(err);
     flight::State w;
     if (!fl->plan) {
         w = *fl->base.st;
         fl->base.st->flags = 0;
     } else {
-        if (hipSetDevice(fl->plan->device) != hipSuccess) return SRT_ERR_HIP;
-        hipStream_t s = fl->plan->stream;
-        if (hipMemcpyAsync(&w, fl->base.st, sizeof w, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            set_err(err, SRT_ERR_HIP, "flight: stream failed");
-            return SRT_ERR_HIP;
-        }
-        if (w.flags) (void)hipMemsetAsync(&fl->base.st->flags, 0, 4, s);
+        if (!stage::use_device(fl->plan)) return SRT_ERR_HIP;
+        const srt_status st = stage::read_status(fl->plan, &w, fl->base.st, sizeof w, err, "flight");
+        if (st != SRT_OK) return st;
     }
     const uint64_t stored = flight::stored(fl->base, w.len);
     fl->bound = stored;

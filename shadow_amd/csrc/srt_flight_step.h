@@ -100,10 +100,7 @@ SRT_HD uint64_t stored(const Ctx &c, uint64_t len) { return len < c.pool_cap ? l
 
 // source host h's segment of the batch, held inside it whatever host_ptr[] says
 SRT_HD void segment(const Ctx &c, uint32_t h, uint32_t &b, uint32_t &e) {
-    const uint32_t lim = c.host_ptr[c.n_src] < c.n_pkts ? c.host_ptr[c.n_src] : c.n_pkts;
-    b = c.host_ptr[h] < lim ? c.host_ptr[h] : lim;
-    e = c.host_ptr[h + 1] < lim ? c.host_ptr[h + 1] : lim;
-    if (e < b) e = b;
+    relay::segment(c.host_ptr, relay::walked(c.host_ptr, c.n_src, c.n_pkts), h, b, e);
 }
 
 // would batch packet p go into the store?  (raises nothing: the device push counts with it first)

@@ -3081,20 +3081,6 @@ hipError_t preload_fw() {
     return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&fill_kernel<uint16_t>));
 }
 
-hipError_t preload_loss();
-hipError_t preload_level();
-hipError_t preload_sssp();
-hipError_t preload_packet();
-hipError_t preload_direct();
-hipError_t preload_events();
-hipError_t preload_inbound();
-hipError_t preload_outbound();
-hipError_t preload_sendbatch();
-hipError_t preload_flight();
-hipError_t preload_deliver();
-hipError_t preload_tracker();
-hipError_t preload_loopback();
-hipError_t preload_pcap();
 hipError_t preload_kernels() {
     hipError_t e = preload_fw();
     if (e == hipSuccess) e = preload_loss();

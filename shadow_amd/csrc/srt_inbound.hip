@@ -37,8 +37,11 @@
 
 #include "srt_inbound_step.h"
 #include "srt_internal.h"
+#include "srt_stage.h"
 
 namespace {
+
+using stage::set_err;
 
 constexpr uint32_t F_BAD_ORDER = 32;  // order[] / dst_ptr[] out of range (internal, reported as invalid)
 
@@ -119,12 +122,6 @@ __global__ __launch_bounds__(256) void inbound_law_kernel(const uint64_t *__rest
     out[i] = tab ? inb::law_increment(tab, counts[i]) : inb::law_increment_f64(counts[i]);
 }
 
-void set_err(srt_err *err, srt_status code, const char *msg) {
-    if (!err) return;
-    err->code = code;
-    std::snprintf(err->msg, sizeof err->msg, "%s", msg);
-}
-
 }  // namespace
 
 struct srt_inbound {
@@ -157,7 +154,7 @@ hipError_t preload_inbound() {
 extern "C" void srt_inbound_destroy(srt_inbound *ib) {
     if (!ib) return;
     if (ib->plan) {
-        (void)hipSetDevice(ib->plan->device);
+        (void)stage::use_device(ib->plan);
         (void)hipStreamSynchronize(ib->plan->stream);
         (void)hipFree(ib->hosts);
         (void)hipFree(ib->ring);
@@ -170,11 +167,8 @@ extern "C" void srt_inbound_destroy(srt_inbound *ib) {
 
 extern "C" srt_status srt_inbound_create(srt_plan *plan, uint32_t n_hosts, const uint64_t *bw_down_bytes_per_s,
                                          uint32_t queue_cap, srt_inbound **out, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!out || (n_hosts && !bw_down_bytes_per_s)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!out || (n_hosts && !bw_down_bytes_per_s)) return stage::null_argument(err);
     *out = nullptr;
     srt_inbound *ib = new (std::nothrow) srt_inbound;
     if (!ib) return SRT_ERR_OOM;
@@ -211,7 +205,7 @@ extern "C" srt_status srt_inbound_create(srt_plan *plan, uint32_t n_hosts, const
     srt::init_wait();
     const size_t ring_bytes = ((size_t)n_hosts * queue_cap + 1) * sizeof(inb::RingEl);
     const size_t host_bytes = ((size_t)n_hosts + 1) * sizeof(inb::Host);
-    bool ok = hipSetDevice(plan->device) == hipSuccess;
+    bool ok = stage::use_device(plan);
     ok = ok && hipMalloc(&ib->hosts, host_bytes) == hipSuccess && hipMalloc(&ib->ring, ring_bytes) == hipSuccess &&
          hipMalloc(&ib->flags, 16) == hipSuccess && hipMalloc(&ib->law_tab, 8 * inb::LAW_TABLE) == hipSuccess;
     ok = ok && hipMemcpy(ib->hosts, ib->h_hosts.data(), (size_t)n_hosts * sizeof(inb::Host), hipMemcpyHostToDevice) ==
@@ -240,12 +234,10 @@ extern "C" srt_status srt_inbound_run(srt_inbound *ib, const uint32_t *d_order, 
                                       uint64_t until_ns, uint64_t bootstrap_end_ns, uint32_t *d_status,
                                       uint64_t *d_forward_ns, srt_inbound_late *d_late, uint32_t late_cap,
                                       uint32_t *d_late_count, uint64_t *seq_base, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
+    stage::begin(err);
     if (!ib || !d_dst_ptr || (late_cap && !d_late) ||
-        (n_pkts && (!d_order || !d_deliver || !d_total_size || !d_status || !d_forward_ns))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+        (n_pkts && (!d_order || !d_deliver || !d_total_size || !d_status || !d_forward_ns)))
+        return stage::null_argument(err);
     if (n_pkts >= 0xffffffffull) {
         set_err(err, SRT_ERR_INVALID, "more than 2^32-2 packets in one batch");
         return SRT_ERR_INVALID;
@@ -255,7 +247,7 @@ extern "C" srt_status srt_inbound_run(srt_inbound *ib, const uint32_t *d_order, 
         return SRT_ERR_INVALID;
     }
     const uint32_t n = (uint32_t)n_pkts;
-    if (ib->plan && hipSetDevice(ib->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    if (ib->plan && !stage::use_device(ib->plan)) return SRT_ERR_HIP;
     if (n > ib->rec_cap) {  // the staged records grow with the largest batch seen
         if (ib->plan) {
             (void)hipStreamSynchronize(ib->plan->stream);
@@ -307,10 +299,7 @@ extern "C" srt_status srt_inbound_run(srt_inbound *ib, const uint32_t *d_order, 
         if (ib->n)
             hipLaunchKernelGGL(inbound_step_kernel, dim3((ib->n + 63) / 64), dim3(64),
                                WIN_CAP * sizeof(inb::Rec), s, c);
-        if (hipGetLastError() != hipSuccess) {
-            set_err(err, SRT_ERR_HIP, "inbound: launch failed");
-            return SRT_ERR_HIP;
-        }
+        if (stage::launched(err, "inbound") != SRT_OK) return SRT_ERR_HIP;
     } else {
         *c.late_count = 0;
         *c.pending = 0;
@@ -336,7 +325,7 @@ srt_status pull(srt_inbound *ib, bool states, uint32_t *flags, uint64_t *pending
     if (!ib->plan) {
         std::memcpy(w, ib->h_flags, sizeof w);
     } else {
-        if (hipSetDevice(ib->plan->device) != hipSuccess) return SRT_ERR_HIP;
+        if (!stage::use_device(ib->plan)) return SRT_ERR_HIP;
         hipStream_t s = ib->plan->stream;
         if (hipMemcpyAsync(w, ib->flags, sizeof w, hipMemcpyDeviceToHost, s) != hipSuccess ||
             (states && ib->n &&
@@ -354,11 +343,8 @@ srt_status pull(srt_inbound *ib, bool states, uint32_t *flags, uint64_t *pending
 }  // namespace
 
 extern "C" srt_status srt_inbound_status(srt_inbound *ib, uint32_t *flags, uint64_t *n_pending, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!ib) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!ib) return stage::null_argument(err);
     uint32_t f = 0;
     uint64_t pending = 0;
     const srt_status st = pull(ib, false, &f, &pending, err);
@@ -381,11 +367,8 @@ extern "C" srt_status srt_inbound_status(srt_inbound *ib, uint32_t *flags, uint6
 }
 
 extern "C" srt_status srt_inbound_state(srt_inbound *ib, srt_inbound_host_state *out, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!ib || (ib->n && !out)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!ib || (ib->n && !out)) return stage::null_argument(err);
     uint32_t f = 0;
     uint64_t pending = 0;
     const srt_status st = pull(ib, true, &f, &pending, err);
@@ -413,18 +396,15 @@ extern "C" srt_status srt_inbound_state(srt_inbound *ib, srt_inbound_host_state 
 
 extern "C" srt_status srt_inbound_control_law(srt_inbound *ib, const uint64_t *counts, uint64_t n, int use_table,
                                               uint64_t *increments, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!ib || (n && (!counts || !increments))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!ib || (n && (!counts || !increments))) return stage::null_argument(err);
     if (!n) return SRT_OK;
     if (!ib->plan) {
         for (uint64_t i = 0; i < n; ++i)
             increments[i] = use_table ? inb::law_increment(ib->law_tab, counts[i]) : inb::law_increment_f64(counts[i]);
         return SRT_OK;
     }
-    if (hipSetDevice(ib->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    if (!stage::use_device(ib->plan)) return SRT_ERR_HIP;
     hipStream_t s = ib->plan->stream;
     uint64_t *d = nullptr;
     if (hipMalloc(&d, 16 * n) != hipSuccess) {

@@ -476,8 +476,22 @@ srt_status routing_build(const srt_csr *g, const uint32_t *nodes, uint32_t n, co
                          uint64_t *min_latency, srt_err *err);
 // waits for a pending srt_init_async (srt_api.cpp)
 void init_wait();
-// loads the code object of every kernel translation unit (srt_init)
+// loads the code object of every kernel translation unit (srt_init): srt_fw.hip's own, then each unit's
 hipError_t preload_kernels();
+hipError_t preload_loss();
+hipError_t preload_level();
+hipError_t preload_sssp();
+hipError_t preload_packet();
+hipError_t preload_direct();
+hipError_t preload_events();
+hipError_t preload_inbound();
+hipError_t preload_outbound();
+hipError_t preload_sendbatch();
+hipError_t preload_flight();
+hipError_t preload_deliver();
+hipError_t preload_tracker();
+hipError_t preload_loopback();
+hipError_t preload_pcap();
 // srt_deliver.hip: the instance's association table as the next launch on its plan's stream sees it
 // (rebuilt on the host and uploaded on the stream when the associations have changed since the last
 // upload: srt_deliver_run's own path), with the instance's plan (nullptr: host-only) and n_hosts

@@ -42,6 +42,7 @@
 
 #include "srt_internal.h"
 #include "srt_loopback_step.h"
+#include "srt_stage.h"
 
 namespace {
 
@@ -49,38 +50,20 @@ static_assert(sizeof(srt_trk_counters) == 80 && sizeof(srt_trk_meta) == 16 && si
                   sizeof(srt_out_pkt) == 32 && sizeof(loopb::State) == 24 && sizeof(loopb::HostSt) == 16,
               "record layouts");
 
-constexpr uint32_t BT = 256;       // threads a workgroup
-constexpr uint32_t ST = 1024;      // threads of the status sum's one workgroup
-constexpr uint32_t WIDE_AVG = 16;  // more packets a host on average: a wave a host
-
-template <uint32_t L>
-__device__ __forceinline__ uint32_t group_add(uint32_t v) {
-#pragma unroll
-    for (uint32_t off = L / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-template <uint32_t L>
-__device__ __forceinline__ void group_sum(tracker::Acc &a) {
-#pragma unroll
-    for (uint32_t j = 0; j < tracker::N_CTR; ++j) {
-        unsigned long long v = a.v[j];
-#pragma unroll
-        for (uint32_t off = L / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        a.v[j] = v;
-    }
-}
+using stage::BT;
+using stage::ST;
+using stage::set_err;
 
 template <uint32_t L>
 __global__ __launch_bounds__(BT) void loopback_run_kernel(const loopb::Ctx c) {
-    const uint64_t g = ((uint64_t)blockIdx.x * BT + threadIdx.x) / L;
-    const uint32_t l = threadIdx.x % L;
-    const bool own = g < c.n_hosts;
-    const uint32_t h = own ? (uint32_t)g : 0u;
+    const stage::Group<L> G(c.n_hosts);
+    const uint32_t l = G.l;
+    const bool own = G.own();
+    const uint32_t h = own ? (uint32_t)G.g : 0u;
     uint32_t b = 0, e = 0;
     uint64_t last = loopb::NONE;
     if (own) {
-        tracker::segment(c.host_ptr, loopb::walked(c), h, b, e);
+        relay::segment(c.host_ptr, loopb::walked(c), h, b, e);
         last = c.hs[h].last_ns;
     }
     // (1) every lane of the wave takes every step: the shuffles are over whole groups
@@ -102,9 +85,8 @@ __global__ __launch_bounds__(BT) void loopback_run_kernel(const loopb::Ctx c) {
         carry = __shfl(gb, L - 1, L);
         if (i < e) loopb::key_store(c, gb, i, e);
     }
-#pragma unroll
-    for (uint32_t off = L / 2; off > 0; off >>= 1) bits |= __shfl_xor(bits, off);
-    n_tasks = group_add<L>(n_tasks);
+    bits = stage::group_or<L>(bits);
+    n_tasks = stage::group_add<L>(n_tasks);
     if (own && l == 0) loopb::scan_done(c, h, b, e, bits, n_tasks);
     __threadfence();
     __syncthreads();  // the keys and instants of the workgroup's hosts are written
@@ -117,9 +99,9 @@ __global__ __launch_bounds__(BT) void loopback_run_kernel(const loopb::Ctx c) {
         if (bits) loopb::emit_flagged(c, i);
         else miss += loopb::emit(c, h, b, e, i, in, out);
     }
-    group_sum<L>(in);  // every lane is here
-    group_sum<L>(out);
-    miss = group_add<L>(miss);
+    stage::group_sum<L>(in.v);  // every lane is here
+    stage::group_sum<L>(out.v);
+    miss = stage::group_add<L>(miss);
     if (own && l == 0) loopb::emit_done(c, h, in, out, bits ? 0 : e - b, miss);
 }
 
@@ -138,12 +120,6 @@ __global__ __launch_bounds__(ST) void loopback_sum_kernel(const loopb::Ctx c) {
         c.st->n_received = a;
         c.st->n_no_socket = b;
     }
-}
-
-void set_err(srt_err *err, srt_status code, const char *msg) {
-    if (!err) return;
-    err->code = code;
-    std::snprintf(err->msg, sizeof err->msg, "%s", msg);
 }
 
 }  // namespace
@@ -172,7 +148,7 @@ hipError_t preload_loopback() {
 extern "C" void srt_loopback_destroy(srt_loopback *lb) {
     if (!lb) return;
     if (lb->plan) {
-        (void)hipSetDevice(lb->plan->device);
+        (void)stage::use_device(lb->plan);
         (void)hipStreamSynchronize(lb->plan->stream);
         (void)hipFree(lb->mem);
         (void)hipFree(lb->scratch);
@@ -182,11 +158,8 @@ extern "C" void srt_loopback_destroy(srt_loopback *lb) {
 
 extern "C" srt_status srt_loopback_create(srt_plan *plan, uint32_t n_hosts, uint32_t qdisc, uint32_t max_sockets,
                                           uint32_t n_slots, srt_loopback **out, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!out) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!out) return stage::null_argument(err);
     *out = nullptr;
     if (n_hosts >= 0x80000000u || n_slots >= 0x80000000u || qdisc > SRT_QDISC_RR || !max_sockets) {
         set_err(err, SRT_ERR_INVALID, "loopback: n_hosts, n_slots (below 2^31), qdisc or max_sockets out of range");
@@ -218,7 +191,7 @@ extern "C" srt_status srt_loopback_create(srt_plan *plan, uint32_t n_hosts, uint
         }
         if (ok) {
             srt::init_wait();
-            ok = hipSetDevice(plan->device) == hipSuccess;
+            ok = stage::use_device(plan);
             ok = ok && hipMalloc(&lb->mem, bytes + 8) == hipSuccess;
             ok = ok && hipMemset(lb->mem, 0, bytes + 8) == hipSuccess;
             if (!ok) {
@@ -269,13 +242,11 @@ extern "C" srt_status srt_loopback_run(srt_loopback *lb, srt_deliver *dl, const 
                                        const srt_trk_meta *d_trk_meta, uint32_t *d_out_index, uint32_t *d_out_socket,
                                        uint64_t *d_out_recv_ns, uint32_t *d_out_user, uint32_t *d_out_status,
                                        srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
+    stage::begin(err);
     if (!lb || !dl || !d_host_ptr ||
         (n_pkts && (!d_pkts || !d_rx_meta || !d_out_index || !d_out_socket || !d_out_recv_ns || !d_out_user ||
-                    !d_out_status))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+                    !d_out_status)))
+        return stage::null_argument(err);
     if (n_pkts >= 0x80000000ull) {
         set_err(err, SRT_ERR_INVALID, "more than 2^31-1 packets in one batch");
         return SRT_ERR_INVALID;
@@ -331,16 +302,10 @@ extern "C" srt_status srt_loopback_run(srt_loopback *lb, srt_deliver *dl, const 
     }
     if (!c.n_hosts) return SRT_OK;
     hipStream_t s = lb->plan->stream;
-    const bool wide = n_pkts > (uint64_t)WIDE_AVG * c.n_hosts;
-    const uint32_t per = wide ? BT / 64 : BT / 8;
-    const uint32_t blocks = (uint32_t)(((uint64_t)c.n_hosts + per - 1) / per);
-    if (wide) hipLaunchKernelGGL(loopback_run_kernel<64>, dim3(blocks), dim3(BT), 0, s, c);
-    else hipLaunchKernelGGL(loopback_run_kernel<8>, dim3(blocks), dim3(BT), 0, s, c);
-    if (hipGetLastError() != hipSuccess) {
-        set_err(err, SRT_ERR_HIP, "loopback: launch failed");
-        return SRT_ERR_HIP;
-    }
-    return SRT_OK;
+    const bool wide = stage::wide(n_pkts, c.n_hosts);
+    stage::launch_grouped(loopback_run_kernel<64>, loopback_run_kernel<8>, wide, stage::host_blocks(c.n_hosts, wide),
+                          BT, s, c);
+    return stage::launched(err, "loopback");
 }
 
 extern "C" srt_status srt_loopback_heartbeat(srt_loopback *lb, const uint32_t *hosts, uint32_t n_sel_hosts,
@@ -348,25 +313,19 @@ extern "C" srt_status srt_loopback_heartbeat(srt_loopback *lb, const uint32_t *h
                                              srt_trk_counters *out_node_in, srt_trk_counters *out_node_out,
                                              srt_trk_counters *out_slot_in, srt_trk_counters *out_slot_out,
                                              srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!lb) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!lb) return stage::null_argument(err);
     return srt::counters_heartbeat(lb->plan, "loopback", lb->base.node_in, lb->rec_bytes, lb->stage.data(),
                                    lb->n_hosts, lb->n_slots, hosts, n_sel_hosts, slots, n_sel_slots, out_node_in,
                                    out_node_out, out_slot_in, out_slot_out, err);
 }
 
 extern "C" srt_status srt_loopback_tasks(srt_loopback *lb, uint64_t *out_tasks, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!lb || (lb->n_hosts && !out_tasks)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!lb || (lb->n_hosts && !out_tasks)) return stage::null_argument(err);
     const loopb::HostSt *hs = lb->base.hs;
     if (lb->plan && lb->n_hosts) {
-        if (hipSetDevice(lb->plan->device) != hipSuccess) return SRT_ERR_HIP;
+        if (!stage::use_device(lb->plan)) return SRT_ERR_HIP;
         hipStream_t s = lb->plan->stream;
         if (hipMemcpyAsync(lb->h_hs.data(), lb->base.hs, 16 * (size_t)lb->n_hosts, hipMemcpyDeviceToHost, s) !=
                 hipSuccess ||
@@ -383,26 +342,17 @@ extern "C" srt_status srt_loopback_tasks(srt_loopback *lb, uint64_t *out_tasks, 
 
 extern "C" srt_status srt_loopback_status(srt_loopback *lb, uint32_t *flags, uint64_t *n_received,
                                           uint64_t *n_no_socket, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!lb) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!lb) return stage::null_argument(err);
     loopb::State w;
     if (!lb->plan) {
         w = *lb->base.st;
         lb->base.st->flags = 0;
     } else {
-        if (hipSetDevice(lb->plan->device) != hipSuccess) return SRT_ERR_HIP;
-        hipStream_t s = lb->plan->stream;
-        hipLaunchKernelGGL(loopback_sum_kernel, dim3(1), dim3(ST), 0, s, lb->base);
-        if (hipMemcpyAsync(&w, lb->base.st, sizeof w, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            (void)hipGetLastError();
-            set_err(err, SRT_ERR_HIP, "loopback: stream failed");
-            return SRT_ERR_HIP;
-        }
-        if (w.flags) (void)hipMemsetAsync(&lb->base.st->flags, 0, 4, s);
+        if (!stage::use_device(lb->plan)) return SRT_ERR_HIP;
+        hipLaunchKernelGGL(loopback_sum_kernel, dim3(1), dim3(ST), 0, lb->plan->stream, lb->base);
+        const srt_status st = stage::read_status(lb->plan, &w, lb->base.st, sizeof w, err, "loopback");
+        if (st != SRT_OK) return st;
     }
     const uint32_t f = w.flags & 7u;
     if (flags) *flags = f;

@@ -92,7 +92,7 @@ struct Ctx {
     uint64_t *out_recv_ns;
 };
 
-SRT_HD uint32_t walked(const Ctx &c) { return c.host_ptr[c.n_hosts] < c.n_pkts ? c.host_ptr[c.n_hosts] : c.n_pkts; }
+SRT_HD uint32_t walked(const Ctx &c) { return relay::walked(c.host_ptr, c.n_hosts, c.n_pkts); }
 
 // The socket-has-data event of packet i of the span beginning at b, `last` being the host's last
 // instant of the earlier calls: F_* bits of what is wrong with it, A_GROUP when it is the first of
@@ -213,7 +213,7 @@ inline void host_run(const Ctx &c) {
     uint64_t n_recv = 0, n_miss = 0;
     for (uint32_t h = 0; h < c.n_hosts; ++h) {
         uint32_t b, e;
-        tracker::segment(c.host_ptr, lim, h, b, e);
+        relay::segment(c.host_ptr, lim, h, b, e);
         const uint64_t last = c.hs[h].last_ns;
         uint32_t bits = 0, n_tasks = 0, gb = b;
         for (uint32_t i = b; i < e; ++i) {

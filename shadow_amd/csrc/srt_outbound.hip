@@ -46,12 +46,14 @@
 
 #include "srt_internal.h"
 #include "srt_outbound_step.h"
+#include "srt_stage.h"
 
 namespace {
 
 using outb::CUR_LDS;
 using outb::LDS_BYTES;
 using outb::WIN_CAP;
+using stage::set_err;
 static_assert(sizeof(outb::Rec) == 32 && sizeof(outb::Cur) == 8 && sizeof(outb::RingEl) == 32 &&
               sizeof(srt_out_pkt) == 32 && sizeof(srt_outbound_late) == 32, "record layouts");
 
@@ -129,12 +131,6 @@ __global__ __launch_bounds__(256) void outbound_cached_seq_kernel(const outb::Ho
     if (h < n_hosts) seq[h] = outb::cached_seq_of(hosts[h]);
 }
 
-void set_err(srt_err *err, srt_status code, const char *msg) {
-    if (!err) return;
-    err->code = code;
-    std::snprintf(err->msg, sizeof err->msg, "%s", msg);
-}
-
 }  // namespace
 
 struct srt_outbound {
@@ -168,7 +164,7 @@ hipError_t preload_outbound() {
 extern "C" void srt_outbound_destroy(srt_outbound *ob) {
     if (!ob) return;
     if (ob->plan) {
-        (void)hipSetDevice(ob->plan->device);
+        (void)stage::use_device(ob->plan);
         (void)hipStreamSynchronize(ob->plan->stream);
         (void)hipFree(ob->hosts);
         (void)hipFree(ob->ring);
@@ -183,11 +179,8 @@ extern "C" void srt_outbound_destroy(srt_outbound *ob) {
 extern "C" srt_status srt_outbound_create(srt_plan *plan, uint32_t n_hosts, const uint64_t *bw_up_bytes_per_s,
                                           uint32_t qdisc, uint32_t max_sockets, uint32_t queue_cap,
                                           srt_outbound **out, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!out || (n_hosts && !bw_up_bytes_per_s)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!out || (n_hosts && !bw_up_bytes_per_s)) return stage::null_argument(err);
     *out = nullptr;
     if (qdisc > SRT_QDISC_RR || !max_sockets || max_sockets >= 0x80000000u || queue_cap >= 0x7ffffffeu) {
         set_err(err, SRT_ERR_INVALID, "outbound: qdisc, max_sockets or queue_cap out of range");
@@ -231,7 +224,7 @@ extern "C" srt_status srt_outbound_create(srt_plan *plan, uint32_t n_hosts, cons
         return SRT_OK;
     }
     srt::init_wait();
-    bool ok = hipSetDevice(plan->device) == hipSuccess;
+    bool ok = stage::use_device(plan);
     ok = ok && hipMalloc(&ob->hosts, ((size_t)n_hosts + 1) * sizeof(outb::Host)) == hipSuccess &&
          hipMalloc(&ob->ring, n_ring * sizeof(outb::RingEl)) == hipSuccess &&
          hipMalloc(&ob->cur, n_cur * sizeof(outb::Cur)) == hipSuccess &&
@@ -263,12 +256,10 @@ extern "C" srt_status srt_outbound_run(srt_outbound *ob, const srt_out_pkt *d_pk
                                        uint32_t *d_status, uint64_t *d_send_ns, uint64_t *d_send_rank,
                                        srt_outbound_late *d_late, uint32_t late_cap, uint32_t *d_late_count,
                                        uint64_t *seq_base, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
+    stage::begin(err);
     if (!ob || !d_host_ptr || (late_cap && !d_late) ||
-        (n_pkts && (!d_pkts || !d_status || !d_send_ns || !d_send_rank))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+        (n_pkts && (!d_pkts || !d_status || !d_send_ns || !d_send_rank)))
+        return stage::null_argument(err);
     if (n_pkts >= 0x80000000ull) {
         set_err(err, SRT_ERR_INVALID, "more than 2^31-1 packets in one batch");
         return SRT_ERR_INVALID;
@@ -278,7 +269,7 @@ extern "C" srt_status srt_outbound_run(srt_outbound *ob, const srt_out_pkt *d_pk
         return SRT_ERR_INVALID;
     }
     const uint32_t n = (uint32_t)n_pkts;
-    if (ob->plan && hipSetDevice(ob->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    if (ob->plan && !stage::use_device(ob->plan)) return SRT_ERR_HIP;
     if (n > ob->link_cap) {  // the links grow with the largest batch seen
         if (ob->plan) {
             (void)hipStreamSynchronize(ob->plan->stream);
@@ -332,10 +323,7 @@ extern "C" srt_status srt_outbound_run(srt_outbound *ob, const srt_out_pkt *d_pk
                            d_send_rank, c.late_count, c.pending);
         if (ob->n)
             hipLaunchKernelGGL(outbound_step_kernel, dim3((ob->n + 63) / 64), dim3(64), LDS_BYTES, s, c);
-        if (hipGetLastError() != hipSuccess) {
-            set_err(err, SRT_ERR_HIP, "outbound: launch failed");
-            return SRT_ERR_HIP;
-        }
+        if (stage::launched(err, "outbound") != SRT_OK) return SRT_ERR_HIP;
     } else {
         *c.late_count = 0;
         *c.pending = 0;
@@ -363,7 +351,7 @@ srt_status pull(srt_outbound *ob, bool states, uint32_t *flags, uint64_t *pendin
     if (!ob->plan) {
         std::memcpy(w, ob->h_flags, sizeof w);
     } else {
-        if (hipSetDevice(ob->plan->device) != hipSuccess) return SRT_ERR_HIP;
+        if (!stage::use_device(ob->plan)) return SRT_ERR_HIP;
         hipStream_t s = ob->plan->stream;
         if (hipMemcpyAsync(w, ob->flags, sizeof w, hipMemcpyDeviceToHost, s) != hipSuccess ||
             (states && ob->n &&
@@ -381,11 +369,8 @@ srt_status pull(srt_outbound *ob, bool states, uint32_t *flags, uint64_t *pendin
 }  // namespace
 
 extern "C" srt_status srt_outbound_status(srt_outbound *ob, uint32_t *flags, uint64_t *n_pending, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!ob) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!ob) return stage::null_argument(err);
     uint32_t f = 0;
     uint64_t pending = 0;
     const srt_status st = pull(ob, false, &f, &pending, err);
@@ -408,11 +393,8 @@ extern "C" srt_status srt_outbound_status(srt_outbound *ob, uint32_t *flags, uin
 }
 
 extern "C" srt_status srt_outbound_state(srt_outbound *ob, srt_outbound_host_state *out, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!ob || (ob->n && !out)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!ob || (ob->n && !out)) return stage::null_argument(err);
     uint32_t f = 0;
     uint64_t pending = 0;
     const srt_status st = pull(ob, true, &f, &pending, err);
@@ -433,22 +415,15 @@ extern "C" srt_status srt_outbound_state(srt_outbound *ob, srt_outbound_host_sta
 }
 
 extern "C" srt_status srt_outbound_cached_seq(srt_outbound *ob, uint64_t *d_seq, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!ob || (ob->n && !d_seq)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!ob || (ob->n && !d_seq)) return stage::null_argument(err);
     if (!ob->n) return SRT_OK;
     if (!ob->plan) {
         for (uint32_t h = 0; h < ob->n; ++h) d_seq[h] = outb::cached_seq_of(ob->hosts[h]);
         return SRT_OK;
     }
-    if (hipSetDevice(ob->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    if (!stage::use_device(ob->plan)) return SRT_ERR_HIP;
     hipLaunchKernelGGL(outbound_cached_seq_kernel, dim3((ob->n + 255) / 256), dim3(256), 0, ob->plan->stream, ob->hosts,
                        ob->n, d_seq);
-    if (hipGetLastError() != hipSuccess) {
-        set_err(err, SRT_ERR_HIP, "outbound: launch failed");
-        return SRT_ERR_HIP;
-    }
-    return SRT_OK;
+    return stage::launched(err, "outbound");
 }

@@ -31,6 +31,7 @@
 
 #include "srt_internal.h"
 #include "srt_pcap_step.h"
+#include "srt_stage.h"
 
 namespace {
 
@@ -42,61 +43,37 @@ static_assert(sizeof(srt_pcap_rec) == 48 && offsetof(srt_pcap_rec, payload_off) 
                   sizeof(pcap::State) == 32,
               "record layouts");
 
-constexpr uint32_t BT = 256;             // threads a workgroup
-constexpr uint32_t ST = 1024;            // threads of the scan's one workgroup
-constexpr uint32_t WIDE_AVG = 16;        // more records a host on average: a wave a host
+using stage::BT;
+using stage::ST;
+using stage::set_err;
 constexpr uint32_t WRITE_BLOCKS = 1u << 20;  // at most, each striding over the tiles
 static_assert(pcap::TILE == BT * 16, "a thread stores 16 bytes of the tile");
 
 template <uint32_t L>
-__device__ __forceinline__ unsigned long long group_add(unsigned long long v) {
-#pragma unroll
-    for (uint32_t off = L / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-template <uint32_t L>
-__device__ __forceinline__ unsigned long long group_max(unsigned long long v) {
-#pragma unroll
-    for (uint32_t off = L / 2; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-template <uint32_t L>
-__device__ __forceinline__ uint32_t group_or(uint32_t v) {
-#pragma unroll
-    for (uint32_t off = L / 2; off > 0; off >>= 1) v |= __shfl_xor(v, off);
-    return v;
-}
-
-template <uint32_t L>
 __global__ __launch_bounds__(BT) void pcap_hosts_kernel(const pcap::Ctx c) {
-    const uint64_t g = ((uint64_t)blockIdx.x * BT + threadIdx.x) / L;
-    const uint32_t l = threadIdx.x % L;
-    const bool own = g < c.n_hosts;
+    const stage::Group<L> G(c.n_hosts);
+    const uint64_t g = G.g;
+    const uint32_t l = G.l;
     pcap::Seg s = {{0, 0}, {0, 0}};
     pcap::HostAcc a = {0, 0, 0, 0};
     uint32_t bits = 0;
     bool on = false;
-    if (own) {
+    if (G.own()) {
         s = pcap::segs(c, (uint32_t)g);
         on = c.enabled[g] != 0;
         if (on) bits = pcap::order_check(c, (uint32_t)g, s, l, L);
     }
-    bits = group_or<L>(bits);  // every lane is here
-    if (own) {
+    bits = stage::group_or<L>(bits);  // every lane is here
+    if (G.own()) {
         if (!on) pcap::merge_disabled(c, s, l, L);
         else if (!(bits & pcap::DECREASES)) pcap::merge_sorted(c, s, l, L, a);
         else if (l == 0) pcap::merge_serial(c, s, a);
     }
-    a.bytes = group_add<L>(a.bytes);
-    a.cnt = (uint32_t)group_add<L>(a.cnt);
-    a.maxt = group_max<L>(a.maxt);
-    a.flags = group_or<L>(a.flags);
-    if (own && l == 0) pcap::host_finish(c, (uint32_t)g, a, bits);
+    a.bytes = stage::group_add<L>(a.bytes);
+    a.cnt = (uint32_t)stage::group_add<L>((unsigned long long)a.cnt);  // summed in 64 bits like the bytes
+    a.maxt = stage::group_max<L>(a.maxt);
+    a.flags = stage::group_or<L>(a.flags);
+    if (G.own() && l == 0) pcap::host_finish(c, (uint32_t)g, a, bits);
 }
 
 __global__ __launch_bounds__(ST) void pcap_scan_kernel(const pcap::Ctx c) {
@@ -126,7 +103,7 @@ __global__ __launch_bounds__(ST) void pcap_scan_kernel(const pcap::Ctx c) {
         carry += all;
         __syncthreads();
     }
-    cnt = group_add<64>(cnt);
+    cnt = stage::group_add<64>(cnt);
     if (lane == 0) csum[w] = cnt;
     __syncthreads();
     if (t == 0) {
@@ -141,11 +118,12 @@ __global__ __launch_bounds__(ST) void pcap_scan_kernel(const pcap::Ctx c) {
 
 template <uint32_t L>
 __global__ __launch_bounds__(BT) void pcap_offsets_kernel(const pcap::Ctx c) {
-    const uint64_t g = ((uint64_t)blockIdx.x * BT + threadIdx.x) / L;
-    const uint32_t l = threadIdx.x % L;
+    const stage::Group<L> G(c.n_hosts);
+    const uint64_t g = G.g;
+    const uint32_t l = G.l;
     uint32_t base = 0, n = 0;
     unsigned long long run = 0;
-    if (g < c.n_hosts) {
+    if (G.own()) {
         const pcap::Seg s = pcap::segs(c, (uint32_t)g);
         base = s.b[0] + s.b[1];
         n = (s.e[0] - s.b[0]) + (s.e[1] - s.b[1]);
@@ -214,12 +192,6 @@ __global__ __launch_bounds__(BT) void pcap_write_kernel(const pcap::Ctx c) {
     }
 }
 
-void set_err(srt_err *err, srt_status code, const char *msg) {
-    if (!err) return;
-    err->code = code;
-    std::snprintf(err->msg, sizeof err->msg, "%s", msg);
-}
-
 }  // namespace
 
 struct srt_pcap {
@@ -267,7 +239,7 @@ extern "C" void srt_pcap_file_header(uint32_t capture_len, uint8_t out[24]) {
 extern "C" void srt_pcap_destroy(srt_pcap *pc) {
     if (!pc) return;
     if (pc->plan) {
-        (void)hipSetDevice(pc->plan->device);
+        (void)stage::use_device(pc->plan);
         (void)hipStreamSynchronize(pc->plan->stream);
         (void)hipFree(pc->mem);
     }
@@ -277,11 +249,8 @@ extern "C" void srt_pcap_destroy(srt_pcap *pc) {
 
 extern "C" srt_status srt_pcap_create(srt_plan *plan, uint32_t n_hosts, uint32_t capture_len, const uint8_t *enabled,
                                       uint64_t rec_cap, uint32_t flags, srt_pcap **out, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!out) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!out) return stage::null_argument(err);
     *out = nullptr;
     if (n_hosts >= 0x80000000u || rec_cap >= 0x80000000ull || (flags & ~SRT_PCAP_TX_FIRST)) {
         set_err(err, SRT_ERR_INVALID, "pcap: n_hosts or rec_cap not below 2^31, or an unknown flag");
@@ -309,7 +278,7 @@ extern "C" srt_status srt_pcap_create(srt_plan *plan, uint32_t n_hosts, uint32_t
     if (ok && !plan) pc->mem = pc->h_mem.data();
     if (ok && plan) {
         srt::init_wait();
-        ok = hipSetDevice(plan->device) == hipSuccess;
+        ok = stage::use_device(plan);
         ok = ok && hipMalloc(&pc->mem, bytes + 8) == hipSuccess;
         ok = ok && hipMemset(pc->mem, 0, bytes + 8) == hipSuccess;
         if (!ok) {
@@ -351,24 +320,15 @@ extern "C" srt_status srt_pcap_create(srt_plan *plan, uint32_t n_hosts, uint32_t
     return SRT_OK;
 }
 
-namespace {
-uint32_t host_blocks(uint32_t n_hosts, bool wide) {
-    const uint32_t per = wide ? BT / 64 : BT / 8;
-    return (uint32_t)(((uint64_t)n_hosts + per - 1) / per);
-}
-}  // namespace
-
 extern "C" srt_status srt_pcap_run(srt_pcap *pc, const srt_pcap_rec *d_tx, const uint32_t *d_tx_idx,
                                    const uint32_t *d_tx_host_ptr, uint64_t n_tx, const srt_pcap_rec *d_rx,
                                    const uint32_t *d_rx_idx, const uint32_t *d_rx_host_ptr, uint64_t n_rx,
                                    const uint8_t *d_payload, uint64_t payload_bytes, uint8_t *d_out, uint64_t out_cap,
                                    uint64_t *d_host_off, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
+    stage::begin(err);
     if (!pc || !d_tx_host_ptr || !d_rx_host_ptr || !d_host_off || (n_tx && !d_tx) || (n_rx && !d_rx) ||
-        (out_cap && !d_out)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+        (out_cap && !d_out))
+        return stage::null_argument(err);
     if (n_tx > pc->rec_cap || n_rx > pc->rec_cap || n_tx + n_rx > pc->rec_cap) {
         set_err(err, SRT_ERR_INVALID, "pcap: n_tx + n_rx exceeds rec_cap");
         return SRT_ERR_INVALID;
@@ -391,19 +351,13 @@ extern "C" srt_status srt_pcap_run(srt_pcap *pc, const srt_pcap_rec *d_tx, const
         pcap::host_run(c);
         return SRT_OK;
     }
-    if (hipSetDevice(pc->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    if (!stage::use_device(pc->plan)) return SRT_ERR_HIP;
     hipStream_t s = pc->plan->stream;
-    const bool wide = n_tx + n_rx > (uint64_t)WIDE_AVG * c.n_hosts;
-    const uint32_t hb = host_blocks(c.n_hosts, wide);
-    if (hb) {
-        if (wide) hipLaunchKernelGGL(pcap_hosts_kernel<64>, dim3(hb), dim3(BT), 0, s, c);
-        else hipLaunchKernelGGL(pcap_hosts_kernel<8>, dim3(hb), dim3(BT), 0, s, c);
-    }
+    const bool wide = stage::wide(n_tx + n_rx, c.n_hosts);
+    const uint32_t hb = stage::host_blocks(c.n_hosts, wide);
+    if (hb) stage::launch_grouped(pcap_hosts_kernel<64>, pcap_hosts_kernel<8>, wide, hb, BT, s, c);
     hipLaunchKernelGGL(pcap_scan_kernel, dim3(1), dim3(ST), 0, s, c);
-    if (hb) {
-        if (wide) hipLaunchKernelGGL(pcap_offsets_kernel<64>, dim3(hb), dim3(BT), 0, s, c);
-        else hipLaunchKernelGGL(pcap_offsets_kernel<8>, dim3(hb), dim3(BT), 0, s, c);
-    }
+    if (hb) stage::launch_grouped(pcap_offsets_kernel<64>, pcap_offsets_kernel<8>, wide, hb, BT, s, c);
     // the call's bytes are at most out_cap (else nothing is written) and at most 16 + min(capture_len, 65535) a record
     const uint64_t per_rec = pcap::REC_HDR + std::min<uint64_t>(pc->capture_len, 65535);
     const uint64_t most = std::min<uint64_t>(out_cap, (n_tx + n_rx) * per_rec);
@@ -412,34 +366,21 @@ extern "C" srt_status srt_pcap_run(srt_pcap *pc, const srt_pcap_rec *d_tx, const
         hipLaunchKernelGGL(pcap_write_kernel, dim3((uint32_t)std::min<uint64_t>(tiles, WRITE_BLOCKS)), dim3(BT), 0, s,
                            c);
     }
-    if (hipGetLastError() != hipSuccess) {
-        set_err(err, SRT_ERR_HIP, "pcap: launch failed");
-        return SRT_ERR_HIP;
-    }
-    return SRT_OK;
+    return stage::launched(err, "pcap");
 }
 
 extern "C" srt_status srt_pcap_status(srt_pcap *pc, uint32_t *flags, uint64_t *n_records, uint64_t *n_bytes,
                                       srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!pc) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!pc) return stage::null_argument(err);
     pcap::State w;
     if (!pc->plan) {
         w = *pc->base.st;
         pc->base.st->flags = 0;
     } else {
-        if (hipSetDevice(pc->plan->device) != hipSuccess) return SRT_ERR_HIP;
-        hipStream_t s = pc->plan->stream;
-        if (hipMemcpyAsync(&w, pc->base.st, sizeof w, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            (void)hipGetLastError();
-            set_err(err, SRT_ERR_HIP, "pcap: stream failed");
-            return SRT_ERR_HIP;
-        }
-        if (w.flags) (void)hipMemsetAsync(&pc->base.st->flags, 0, 4, s);
+        if (!stage::use_device(pc->plan)) return SRT_ERR_HIP;
+        const srt_status st = stage::read_status(pc->plan, &w, pc->base.st, sizeof w, err, "pcap");
+        if (st != SRT_OK) return st;
     }
     const uint32_t f = w.flags & 31u;
     if (flags) *flags = f;
@@ -459,11 +400,8 @@ extern "C" srt_status srt_pcap_status(srt_pcap *pc, uint32_t *flags, uint64_t *n
 }
 
 extern "C" srt_status srt_pcap_open_files(srt_pcap *pc, const char *const *paths, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!pc || (pc->n_hosts && !paths)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!pc || (pc->n_hosts && !paths)) return stage::null_argument(err);
     close_files(pc);
     try {
         pc->files.assign(pc->n_hosts, nullptr);
@@ -491,11 +429,8 @@ extern "C" srt_status srt_pcap_open_files(srt_pcap *pc, const char *const *paths
 
 extern "C" srt_status srt_pcap_append_files(srt_pcap *pc, const uint64_t *host_off, const uint8_t *bytes,
                                             srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!pc || !host_off) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!pc || !host_off) return stage::null_argument(err);
     if (pc->files.size() != pc->n_hosts) {
         set_err(err, SRT_ERR_INVALID, "pcap: no files are open");
         return SRT_ERR_INVALID;

@@ -94,10 +94,7 @@ struct HostAcc {
     uint32_t cnt, flags;
 };
 
-SRT_HD uint32_t walked(const Ctx &c, uint32_t side) {
-    const uint32_t v = c.ptr[side][c.n_hosts];
-    return v < c.n[side] ? v : c.n[side];
-}
+SRT_HD uint32_t walked(const Ctx &c, uint32_t side) { return relay::walked(c.ptr[side], c.n_hosts, c.n[side]); }
 
 // host h's segments of the two lists, held below the lists' lengths whatever ptr[] says
 SRT_HD Seg segs(const Ctx &c, uint32_t h) {

@@ -1,7 +1,10 @@
-// srt_relay_common.h -- what the inbound and the outbound relay steps share
-// (srt_inbound_step.h, srt_outbound_step.h): the saturating u64 arithmetic of
-// the reference's SimulationTime / token counts, the host-or-device updates of
-// the call-wide words, and the relay's TokenBucket.
+// srt_relay_common.h -- what the packet stages' step headers (srt_*_step.h)
+// share, written once for the host and the device: the saturating u64
+// arithmetic of the reference's SimulationTime / token counts, the
+// host-or-device updates of the call-wide words, the walk of a grouped batch
+// (a host's segment, the late list's length, the scan's clamped base), and the
+// relays' TokenBucket.  Plain host compilers build it for tests/asan: nothing
+// HIP-only outside SRT_HD and __HIP_DEVICE_COMPILE__.
 //
 // Reference: src/main/network/relay/token_bucket.rs (lazy_refill,
 // conforming_remove, compute_conforming_duration) as sized by
@@ -54,6 +57,29 @@ SRT_HD uint32_t take_slot(uint32_t *count) {
     return (*count)++;
 #endif
 }
+
+// ---- the walk of a batch grouped by host: ptr[0 .. n_hosts] are the hosts' bounds
+// the packets the bounds cover, held inside the batch of n whatever ptr[] says
+SRT_HD uint32_t walked(const uint32_t *ptr, uint32_t n_hosts, uint32_t n) {
+    return ptr[n_hosts] < n ? ptr[n_hosts] : n;
+}
+
+// host h's segment, held below `lim` (walked) whatever ptr[] says
+SRT_HD void segment(const uint32_t *ptr, uint32_t lim, uint32_t h, uint32_t &b, uint32_t &e) {
+    b = ptr[h] < lim ? ptr[h] : lim;
+    e = ptr[h + 1] < lim ? ptr[h + 1] : lim;
+    if (e < b) e = b;
+}
+
+// records of a late list that exist: the count runs past the cap on overflow (nullptr: no late list)
+SRT_HD uint32_t late_n(const uint32_t *count, uint32_t cap) {
+    if (!count) return 0;
+    const uint32_t n = *count;
+    return n < cap ? n : cap;
+}
+
+// the scan's output for a host whose packets begin at `prefix`: positions stop at out_cap (a u32)
+SRT_HD uint32_t host_base(uint64_t prefix, uint64_t out_cap) { return (uint32_t)(prefix < out_cap ? prefix : out_cap); }
 
 // create_token_bucket's refill size (relay/mod.rs:277-287); the capacity is sat_add(refill, MTU)
 SRT_HD uint64_t bucket_refill(uint64_t bytes_per_second) { return bytes_per_second / 1000 ? bytes_per_second / 1000 : 1; }

@@ -33,27 +33,26 @@
 
 #include "srt_internal.h"
 #include "srt_sendbatch_step.h"
+#include "srt_stage.h"
 
 namespace {
 
 static_assert(sizeof(srt_send_meta) == 16 && sizeof(srt_pkt) == 24 && sizeof(srt_outbound_late) == 32,
               "record layouts");
 
-constexpr uint32_t BT = 256;            // threads a workgroup of (1), (2) and (4)
-constexpr uint32_t ST = 1024;           // threads of the scan's one workgroup
-constexpr uint32_t LATE_BLOCKS = 1024;  // at most, each striding over the late list
-constexpr uint32_t WIDE_AVG = 16;       // more packets a host on average: a wave a host
+using stage::BT;
+using stage::ST;
+using stage::set_err;
 
 template <uint32_t L>
 __global__ __launch_bounds__(BT) void sendbatch_count_kernel(const sendb::Ctx c) {
-    const uint64_t g = ((uint64_t)blockIdx.x * BT + threadIdx.x) / L;
-    const uint32_t l = threadIdx.x % L;
+    const stage::Group<L> G(c.n_hosts);
     uint32_t n = 0;
     uint64_t mn = sendb::NONE;
-    if (g < c.n_hosts) {
+    if (G.own()) {
         uint32_t b, e;
-        sendb::segment(c, (uint32_t)g, b, e);
-        for (uint32_t i = b + l; i < e; i += L) {
+        sendb::segment(c, (uint32_t)G.g, b, e);
+        for (uint32_t i = b + G.l; i < e; i += L) {
             const uint64_t rank = c.send_rank[i];
             if (rank == sendb::NONE) {
                 sendb::log_keep(c, i);
@@ -63,76 +62,48 @@ __global__ __launch_bounds__(BT) void sendbatch_count_kernel(const sendb::Ctx c)
             }
         }
     }
-    // every lane is here: the group's lanes hold its partial counts and minima
+    // every lane is here: the group's lanes hold its partial counts and minima (one fused walk of the lanes:
+    // two separate reductions schedule differently)
     for (uint32_t off = L / 2; off > 0; off >>= 1) {
         n += __shfl_xor(n, off);
         const unsigned long long o = __shfl_xor((unsigned long long)mn, off);
         mn = o < mn ? o : mn;
     }
-    if (g < c.n_hosts && l == 0) {
-        c.cnt[g] = n;
-        c.first[g] = mn;
+    if (G.own() && G.l == 0) {
+        c.cnt[G.g] = n;
+        c.first[G.g] = mn;
     }
 }
 
 __global__ __launch_bounds__(BT) void sendbatch_late_kernel(const sendb::Ctx c) {
-    const uint32_t n = sendb::late_n(c);
-    for (uint64_t k = (uint64_t)blockIdx.x * BT + threadIdx.x; k < n; k += (uint64_t)gridDim.x * BT)
-        sendb::count_late(c, (uint32_t)k);
+    for (uint64_t k : stage::grid_stride(sendb::late_n(c))) sendb::count_late(c, (uint32_t)k);
 }
 
 __global__ __launch_bounds__(ST) void sendbatch_scan_kernel(const sendb::Ctx c) {
-    __shared__ uint64_t wsum[ST / 64];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (uint32_t)(((uint64_t)c.n_hosts + ST - 1) / ST);  // below 2^22: t * per fits
-    const uint64_t b64 = (uint64_t)t * per;
-    const uint32_t b = b64 < c.n_hosts ? (uint32_t)b64 : c.n_hosts;
-    const uint32_t e = b64 + per < c.n_hosts ? (uint32_t)(b64 + per) : c.n_hosts;
-    uint64_t sum = 0;
-    for (uint32_t h = b; h < e; ++h) sum += c.cnt[h];
-    // inclusive scan of the threads' sums: within the wave, then over the waves' totals
-    uint64_t inc = sum;
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-        const unsigned long long o = __shfl_up((unsigned long long)inc, off);
-        if ((t & 63) >= off) inc += o;
-    }
-    if ((t & 63) == 63) wsum[t >> 6] = inc;
-    __syncthreads();
-    uint64_t before = 0;
-    for (uint32_t w = 0; w < (t >> 6); ++w) before += wsum[w];
-    uint64_t run = before + inc - sum;
-    for (uint32_t h = b; h < e; ++h) {
-        const uint32_t n = c.cnt[h];
-        c.out_host_ptr[h] = sendb::host_base(c, run);
-        run += n;
-    }
-    if (t == ST - 1) sendb::scan_end(c, before + inc);
+    stage::scan_hosts<ST>(
+        c.n_hosts, [&](uint32_t h) { return c.cnt[h]; },
+        [&](uint32_t h, uint64_t run) {
+            const uint32_t n = c.cnt[h];
+            c.out_host_ptr[h] = sendb::host_base(c, run);
+            return n;
+        },
+        [&](uint64_t total) { sendb::scan_end(c, total); });
 }
 
 template <uint32_t L>
 __global__ __launch_bounds__(BT) void sendbatch_scatter_kernel(const sendb::Ctx c, uint32_t host_blocks) {
     if (blockIdx.x < host_blocks) {
-        const uint64_t g = ((uint64_t)blockIdx.x * BT + threadIdx.x) / L;
-        const uint32_t l = threadIdx.x % L;
-        if (g >= c.n_hosts) return;
-        const uint32_t h = (uint32_t)g;
+        const stage::Group<L> G(c.n_hosts);
+        if (!G.own()) return;
+        const uint32_t h = (uint32_t)G.g;
         uint32_t b, e;
         sendb::segment(c, h, b, e);
-        if (b + l >= e) return;
+        if (b + G.l >= e) return;
         const sendb::HostRun hr = sendb::host_run(c, h);
-        for (uint32_t i = b + l; i < e; i += L) sendb::scatter_batch(c, hr, h, i);
+        for (uint32_t i = b + G.l; i < e; i += L) sendb::scatter_batch(c, hr, h, i);
     } else {
-        const uint32_t n = sendb::late_n(c);
-        const uint64_t stride = (uint64_t)(gridDim.x - host_blocks) * BT;
-        for (uint64_t k = (uint64_t)(blockIdx.x - host_blocks) * BT + threadIdx.x; k < n; k += stride)
-            sendb::scatter_late(c, (uint32_t)k);
+        for (uint64_t k : stage::grid_stride(sendb::late_n(c), host_blocks)) sendb::scatter_late(c, (uint32_t)k);
     }
-}
-
-void set_err(srt_err *err, srt_status code, const char *msg) {
-    if (!err) return;
-    err->code = code;
-    std::snprintf(err->msg, sizeof err->msg, "%s", msg);
 }
 
 }  // namespace
@@ -163,7 +134,7 @@ hipError_t preload_sendbatch() {
 extern "C" void srt_sendbatch_destroy(srt_sendbatch *sb) {
     if (!sb) return;
     if (sb->plan) {
-        (void)hipSetDevice(sb->plan->device);
+        (void)stage::use_device(sb->plan);
         (void)hipStreamSynchronize(sb->plan->stream);
         (void)hipFree(sb->log);
         (void)hipFree(sb->cnt);
@@ -175,11 +146,8 @@ extern "C" void srt_sendbatch_destroy(srt_sendbatch *sb) {
 
 extern "C" srt_status srt_sendbatch_create(srt_plan *plan, uint32_t n_hosts, uint64_t log_cap, srt_sendbatch **out,
                                            srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!out) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!out) return stage::null_argument(err);
     *out = nullptr;
     if (n_hosts == 0xffffffffu || log_cap > (1ull << 40)) {
         set_err(err, SRT_ERR_INVALID, "sendbatch: n_hosts or log_cap out of range");
@@ -209,7 +177,7 @@ extern "C" srt_status srt_sendbatch_create(srt_plan *plan, uint32_t n_hosts, uin
         return SRT_OK;
     }
     srt::init_wait();
-    bool ok = hipSetDevice(plan->device) == hipSuccess;
+    bool ok = stage::use_device(plan);
     ok = ok && hipMalloc(&sb->log, n_log * sizeof(srt_send_meta)) == hipSuccess &&
          hipMalloc(&sb->cnt, n_host * 4) == hipSuccess && hipMalloc(&sb->first, n_host * 8) == hipSuccess &&
          hipMalloc(&sb->flags, 16) == hipSuccess;
@@ -236,12 +204,10 @@ extern "C" srt_status srt_sendbatch_run(srt_sendbatch *sb, const uint32_t *d_hos
                                         const srt_outbound_late *d_late, uint32_t late_cap,
                                         const uint32_t *d_late_count, srt_pkt *d_out_pkts, uint32_t *d_out_host_ptr,
                                         uint32_t *d_out_user, uint64_t *d_out_seq, uint64_t out_cap, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
+    stage::begin(err);
     if (!sb || !d_host_ptr || !d_out_host_ptr || (n_pkts && (!d_meta || !d_send_ns || !d_send_rank)) ||
-        (late_cap && (!d_late || !d_late_count)) || (out_cap && (!d_out_pkts || !d_out_user || !d_out_seq))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+        (late_cap && (!d_late || !d_late_count)) || (out_cap && (!d_out_pkts || !d_out_user || !d_out_seq)))
+        return stage::null_argument(err);
     if (n_pkts >= 0x80000000ull || late_cap >= 0x80000000u) {
         set_err(err, SRT_ERR_INVALID, "more than 2^31-1 packets in one batch or late list");
         return SRT_ERR_INVALID;
@@ -303,52 +269,32 @@ extern "C" srt_status srt_sendbatch_run(srt_sendbatch *sb, const uint32_t *d_hos
         for (uint32_t k = 0; k < n_late; ++k) sendb::scatter_late(c, k);
         return SRT_OK;
     }
-    if (hipSetDevice(sb->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    if (!stage::use_device(sb->plan)) return SRT_ERR_HIP;
     hipStream_t s = sb->plan->stream;
-    const bool wide = n_pkts > (uint64_t)WIDE_AVG * c.n_hosts;
-    const uint32_t per_block = wide ? BT / 64 : BT / 8;
-    const uint32_t host_blocks = (uint32_t)(((uint64_t)c.n_hosts + per_block - 1) / per_block);
-    const uint32_t late_blocks = late_cap ? std::min<uint32_t>((late_cap + BT - 1) / BT, LATE_BLOCKS) : 0;
-    if (host_blocks) {
-        if (wide) hipLaunchKernelGGL(sendbatch_count_kernel<64>, dim3(host_blocks), dim3(BT), 0, s, c);
-        else hipLaunchKernelGGL(sendbatch_count_kernel<8>, dim3(host_blocks), dim3(BT), 0, s, c);
-    }
+    const bool wide = stage::wide(n_pkts, c.n_hosts);
+    const uint32_t host_blocks = stage::host_blocks(c.n_hosts, wide);
+    const uint32_t late_blocks = stage::strided_blocks(late_cap, stage::LATE_BLOCKS);
+    if (host_blocks)
+        stage::launch_grouped(sendbatch_count_kernel<64>, sendbatch_count_kernel<8>, wide, host_blocks, BT, s, c);
     if (late_blocks) hipLaunchKernelGGL(sendbatch_late_kernel, dim3(late_blocks), dim3(BT), 0, s, c);
     hipLaunchKernelGGL(sendbatch_scan_kernel, dim3(1), dim3(ST), 0, s, c);
-    if (host_blocks + late_blocks) {
-        if (wide)
-            hipLaunchKernelGGL(sendbatch_scatter_kernel<64>, dim3(host_blocks + late_blocks), dim3(BT), 0, s, c,
-                               host_blocks);
-        else
-            hipLaunchKernelGGL(sendbatch_scatter_kernel<8>, dim3(host_blocks + late_blocks), dim3(BT), 0, s, c,
-                               host_blocks);
-    }
-    if (hipGetLastError() != hipSuccess) {
-        set_err(err, SRT_ERR_HIP, "sendbatch: launch failed");
-        return SRT_ERR_HIP;
-    }
-    return SRT_OK;
+    if (host_blocks + late_blocks)
+        stage::launch_grouped(sendbatch_scatter_kernel<64>, sendbatch_scatter_kernel<8>, wide,
+                              host_blocks + late_blocks, BT, s, c, host_blocks);
+    return stage::launched(err, "sendbatch");
 }
 
 extern "C" srt_status srt_sendbatch_status(srt_sendbatch *sb, uint32_t *flags, uint64_t *n_sent, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!sb) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!sb) return stage::null_argument(err);
     uint32_t w[4] = {0, 0, 0, 0};
     if (!sb->plan) {
         std::memcpy(w, sb->h_flags, sizeof w);
         sb->h_flags[0] = 0;
     } else {
-        if (hipSetDevice(sb->plan->device) != hipSuccess) return SRT_ERR_HIP;
-        hipStream_t s = sb->plan->stream;
-        if (hipMemcpyAsync(w, sb->flags, sizeof w, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            set_err(err, SRT_ERR_HIP, "sendbatch: stream failed");
-            return SRT_ERR_HIP;
-        }
-        if (w[0]) (void)hipMemsetAsync(sb->flags, 0, 4, s);
+        if (!stage::use_device(sb->plan)) return SRT_ERR_HIP;
+        const srt_status st = stage::read_status(sb->plan, w, sb->flags, sizeof w, err, "sendbatch");
+        if (st != SRT_OK) return st;
     }
     const uint32_t f = w[0] & 15u;
     if (flags) *flags = f;

@@ -60,19 +60,11 @@ struct Ctx {
     uint32_t n_hosts, n_pkts, late_cap, pad;
 };
 
-// records of the late list that exist: the count runs past the cap on overflow
-SRT_HD uint32_t late_n(const Ctx &c) {
-    if (!c.late_count) return 0;
-    const uint32_t n = *c.late_count;
-    return n < c.late_cap ? n : c.late_cap;
-}
+SRT_HD uint32_t late_n(const Ctx &c) { return relay::late_n(c.late_count, c.late_cap); }
 
-// host h's segment of the batch, held inside it whatever host_ptr[] says
+// host h's segment of the batch
 SRT_HD void segment(const Ctx &c, uint32_t h, uint32_t &b, uint32_t &e) {
-    const uint32_t lim = c.host_ptr[c.n_hosts] < c.n_pkts ? c.host_ptr[c.n_hosts] : c.n_pkts;
-    b = c.host_ptr[h] < lim ? c.host_ptr[h] : lim;
-    e = c.host_ptr[h + 1] < lim ? c.host_ptr[h + 1] : lim;
-    if (e < b) e = b;
+    relay::segment(c.host_ptr, relay::walked(c.host_ptr, c.n_hosts, c.n_pkts), h, b, e);
 }
 
 // the log slot of the seq that lies `a` before the end of the call's range, 0 <= a <= log_cap
@@ -103,7 +95,7 @@ SRT_HD void count_late(const Ctx &c, uint32_t k) {
 }
 
 // the scan's output for a host whose packets begin at `prefix` of `total` sent
-SRT_HD uint32_t host_base(const Ctx &c, uint64_t prefix) { return (uint32_t)(prefix < c.out_cap ? prefix : c.out_cap); }
+SRT_HD uint32_t host_base(const Ctx &c, uint64_t prefix) { return relay::host_base(prefix, c.out_cap); }
 
 SRT_HD void scan_end(const Ctx &c, uint64_t total) {
     c.out_host_ptr[c.n_hosts] = host_base(c, total);

@@ -38,6 +38,7 @@
 
 #include "srt_internal.h"
 #include "srt_tracker_step.h"
+#include "srt_stage.h"
 
 namespace {
 
@@ -45,23 +46,9 @@ static_assert(sizeof(srt_trk_counters) == 80 && sizeof(srt_trk_meta) == 16 && si
                   sizeof(srt_outbound_late) == 32,
               "record layouts");
 
-constexpr uint32_t BT = 256;            // threads a workgroup
-constexpr uint32_t ST = 1024;           // threads of the status sum's one workgroup
-constexpr uint32_t LATE_BLOCKS = 1024;  // at most, each striding over the late list or the flat records
-constexpr uint32_t NOTE_BLOCKS = 4096;  // at most, each striding over the note
-constexpr uint32_t WIDE_AVG = 16;       // more packets a host on average: a wave a host
-
-// the sums of the group's L lanes, in every one of them
-template <uint32_t L>
-__device__ __forceinline__ void group_sum(tracker::Acc &a) {
-#pragma unroll
-    for (uint32_t j = 0; j < tracker::N_CTR; ++j) {
-        unsigned long long v = a.v[j];
-#pragma unroll
-        for (uint32_t off = L / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        a.v[j] = v;
-    }
-}
+using stage::BT;
+using stage::ST;
+using stage::set_err;
 
 __global__ __launch_bounds__(BT) void tracker_note_kernel(const tracker::Ctx c) {
     for (uint64_t i = (uint64_t)c.note_first + (uint64_t)blockIdx.x * BT + threadIdx.x; i < c.note_n;
@@ -70,47 +57,40 @@ __global__ __launch_bounds__(BT) void tracker_note_kernel(const tracker::Ctx c) 
 }
 
 __global__ __launch_bounds__(BT) void tracker_late_kernel(const tracker::Ctx c) {
-    const uint32_t n = tracker::late_n(c);
-    for (uint64_t k = (uint64_t)blockIdx.x * BT + threadIdx.x; k < n; k += (uint64_t)gridDim.x * BT)
-        tracker::tx_late(c, (uint32_t)k);
+    for (uint64_t k : stage::grid_stride(tracker::late_n(c))) tracker::tx_late(c, (uint32_t)k);
 }
 
 template <uint32_t L>
 __global__ __launch_bounds__(BT) void tracker_tx_kernel(const tracker::Ctx c) {
-    const uint64_t g = ((uint64_t)blockIdx.x * BT + threadIdx.x) / L;
-    const uint32_t l = threadIdx.x % L;
-    const bool own = g < c.n_hosts;
+    const stage::Group<L> G(c.n_hosts);
     tracker::Acc a;
     tracker::acc_zero(a);
-    if (own) {
+    if (G.own()) {
         uint32_t b, e;
-        tracker::segment(c.host_ptr, tracker::tx_walked(c), (uint32_t)g, b, e);
-        for (uint32_t i = b + l; i < e; i += L) tracker::tx_batch(c, i, a);
-        if (l == 0) tracker::tx_cached(c, (uint32_t)g, a);
+        tracker::segment(c.host_ptr, tracker::tx_walked(c), (uint32_t)G.g, b, e);
+        for (uint32_t i = b + G.l; i < e; i += L) tracker::tx_batch(c, i, a);
+        if (G.l == 0) tracker::tx_cached(c, (uint32_t)G.g, a);
     }
-    group_sum<L>(a);  // every lane is here
-    if (own && l == 0) tracker::host_merge(c.node_out + g, c.cnt_tx + g, a);
+    stage::group_sum<L>(a.v);  // every lane is here
+    if (G.own() && G.l == 0) tracker::host_merge(c.node_out + G.g, c.cnt_tx + G.g, a);
 }
 
 template <uint32_t L>
 __global__ __launch_bounds__(BT) void tracker_rx_kernel(const tracker::Ctx c) {
-    const uint64_t g = ((uint64_t)blockIdx.x * BT + threadIdx.x) / L;
-    const uint32_t l = threadIdx.x % L;
-    const bool own = g < c.n_hosts;
+    const stage::Group<L> G(c.n_hosts);
     tracker::Acc a;
     tracker::acc_zero(a);
-    if (own) {
+    if (G.own()) {
         uint32_t b, e;
-        tracker::segment(c.out_host_ptr, tracker::rx_walked(c), (uint32_t)g, b, e);
-        for (uint32_t p = b + l; p < e; p += L) tracker::rx_record(c, p, a);
+        tracker::segment(c.out_host_ptr, tracker::rx_walked(c), (uint32_t)G.g, b, e);
+        for (uint32_t p = b + G.l; p < e; p += L) tracker::rx_record(c, p, a);
     }
-    group_sum<L>(a);
-    if (own && l == 0) tracker::host_merge(c.node_in + g, c.cnt_rx + g, a);
+    stage::group_sum<L>(a.v);
+    if (G.own() && G.l == 0) tracker::host_merge(c.node_in + G.g, c.cnt_rx + G.g, a);
 }
 
 __global__ __launch_bounds__(BT) void tracker_flat_kernel(const tracker::Ctx c) {
-    for (uint64_t k = (uint64_t)blockIdx.x * BT + threadIdx.x; k < c.f_n; k += (uint64_t)gridDim.x * BT)
-        tracker::rx_flat(c, (uint32_t)k);
+    for (uint64_t k : stage::grid_stride(c.f_n)) tracker::rx_flat(c, (uint32_t)k);
 }
 
 // srt_tracker_status: the hosts' counts of packets, summed by one workgroup
@@ -128,12 +108,6 @@ __global__ __launch_bounds__(ST) void tracker_sum_kernel(const tracker::Ctx c) {
         c.st->n_tx = a;
         c.st->n_rx = b;
     }
-}
-
-void set_err(srt_err *err, srt_status code, const char *msg) {
-    if (!err) return;
-    err->code = code;
-    std::snprintf(err->msg, sizeof err->msg, "%s", msg);
 }
 
 }  // namespace
@@ -161,7 +135,7 @@ hipError_t preload_tracker() {
 extern "C" void srt_tracker_destroy(srt_tracker *trk) {
     if (!trk) return;
     if (trk->plan) {
-        (void)hipSetDevice(trk->plan->device);
+        (void)stage::use_device(trk->plan);
         (void)hipStreamSynchronize(trk->plan->stream);
         (void)hipFree(trk->mem);
     }
@@ -170,11 +144,8 @@ extern "C" void srt_tracker_destroy(srt_tracker *trk) {
 
 extern "C" srt_status srt_tracker_create(srt_plan *plan, uint32_t n_hosts, uint32_t n_sockets, uint64_t note_cap,
                                          uint64_t log_cap, srt_tracker **out, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!out) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!out) return stage::null_argument(err);
     *out = nullptr;
     if (n_hosts >= 0x80000000u || n_sockets >= 0x80000000u || note_cap > (1ull << 31) || log_cap > (1ull << 31)) {
         set_err(err, SRT_ERR_INVALID,
@@ -208,7 +179,7 @@ extern "C" srt_status srt_tracker_create(srt_plan *plan, uint32_t n_hosts, uint3
         }
         if (ok) {
             srt::init_wait();
-            ok = hipSetDevice(plan->device) == hipSuccess;
+            ok = stage::use_device(plan);
             ok = ok && hipMalloc(&trk->mem, bytes + 8) == hipSuccess;
             ok = ok && hipMemset(trk->mem, 0, bytes + 8) == hipSuccess;
             if (!ok) {
@@ -253,32 +224,14 @@ extern "C" srt_status srt_tracker_create(srt_plan *plan, uint32_t n_hosts, uint3
     return SRT_OK;
 }
 
-namespace {
-srt_status launched(srt_err *err) {
-    if (hipGetLastError() != hipSuccess) {
-        set_err(err, SRT_ERR_HIP, "tracker: launch failed");
-        return SRT_ERR_HIP;
-    }
-    return SRT_OK;
-}
-
-// blocks of the hosts' walk: BT / L hosts each
-uint32_t host_blocks(uint32_t n_hosts, bool wide) {
-    const uint32_t per = wide ? BT / 64 : BT / 8;
-    return (uint32_t)(((uint64_t)n_hosts + per - 1) / per);
-}
-}  // namespace
-
 extern "C" srt_status srt_tracker_tx(srt_tracker *trk, const uint64_t *d_cached_seq, const uint32_t *d_host_ptr,
                                      uint64_t n_pkts, const srt_trk_meta *d_meta, const uint32_t *d_status,
                                      uint64_t seq_base, const srt_outbound_late *d_late, uint32_t late_cap,
                                      const uint32_t *d_late_count, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
+    stage::begin(err);
     if (!trk || !d_host_ptr || (trk->n_hosts && !d_cached_seq) || (n_pkts && (!d_meta || !d_status)) ||
-        (late_cap && (!d_late || !d_late_count))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+        (late_cap && (!d_late || !d_late_count)))
+        return stage::null_argument(err);
     if (n_pkts >= 0x80000000ull || late_cap >= 0x80000000u || seq_base + n_pkts < seq_base) {
         set_err(err, SRT_ERR_INVALID, "more than 2^31-1 packets in one batch or late list");
         return SRT_ERR_INVALID;
@@ -299,26 +252,23 @@ extern "C" srt_status srt_tracker_tx(srt_tracker *trk, const uint64_t *d_cached_
         tracker::host_tx(c);
         return SRT_OK;
     }
-    if (hipSetDevice(trk->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    if (!stage::use_device(trk->plan)) return SRT_ERR_HIP;
     hipStream_t s = trk->plan->stream;
     if (late_cap)
-        hipLaunchKernelGGL(tracker_late_kernel, dim3(std::min<uint32_t>((late_cap + BT - 1) / BT, LATE_BLOCKS)),
-                           dim3(BT), 0, s, c);
+        hipLaunchKernelGGL(tracker_late_kernel, dim3(stage::strided_blocks(late_cap, stage::LATE_BLOCKS)), dim3(BT), 0,
+                           s, c);
     if (c.n_hosts) {
-        const bool wide = n_pkts > (uint64_t)WIDE_AVG * c.n_hosts;
-        if (wide) hipLaunchKernelGGL(tracker_tx_kernel<64>, dim3(host_blocks(c.n_hosts, true)), dim3(BT), 0, s, c);
-        else hipLaunchKernelGGL(tracker_tx_kernel<8>, dim3(host_blocks(c.n_hosts, false)), dim3(BT), 0, s, c);
+        const bool wide = stage::wide(n_pkts, c.n_hosts);
+        stage::launch_grouped(tracker_tx_kernel<64>, tracker_tx_kernel<8>, wide, stage::host_blocks(c.n_hosts, wide),
+                              BT, s, c);
     }
-    return launched(err);
+    return stage::launched(err, "tracker");
 }
 
 extern "C" srt_status srt_tracker_note(srt_tracker *trk, const srt_trk_meta *d_meta, uint64_t n_pkts,
                                        uint64_t tag_base, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!trk || (n_pkts && !d_meta)) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!trk || (n_pkts && !d_meta)) return stage::null_argument(err);
     if (n_pkts >= 0x80000000ull || tag_base < trk->note_end || tag_base + n_pkts < tag_base) {
         set_err(err, SRT_ERR_INVALID, "tracker: more than 2^31-1 packets in one note, or tag_base below the previous note's end");
         return SRT_ERR_INVALID;
@@ -334,20 +284,18 @@ extern "C" srt_status srt_tracker_note(srt_tracker *trk, const srt_trk_meta *d_m
         tracker::host_note(c);
         return SRT_OK;
     }
-    if (hipSetDevice(trk->plan->device) != hipSuccess) return SRT_ERR_HIP;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_pkts - c.note_first + BT - 1) / BT, NOTE_BLOCKS);
-    hipLaunchKernelGGL(tracker_note_kernel, dim3(blocks), dim3(BT), 0, trk->plan->stream, c);
-    return launched(err);
+    if (!stage::use_device(trk->plan)) return SRT_ERR_HIP;
+    hipLaunchKernelGGL(tracker_note_kernel, dim3(stage::strided_blocks(n_pkts - c.note_first, stage::NOTE_BLOCKS)),
+                       dim3(BT), 0, trk->plan->stream, c);
+    return stage::launched(err, "tracker");
 }
 
 extern "C" srt_status srt_tracker_rx(srt_tracker *trk, const uint32_t *d_out_host_ptr, const uint32_t *d_out_socket,
                                      const uint64_t *d_out_tag, const uint32_t *d_out_status, uint64_t out_cap,
                                      srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!trk || !d_out_host_ptr || (out_cap && (!d_out_socket || !d_out_tag || !d_out_status))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!trk || !d_out_host_ptr || (out_cap && (!d_out_socket || !d_out_tag || !d_out_status)))
+        return stage::null_argument(err);
     tracker::Ctx c = trk->base;
     c.note_end = trk->note_end;
     c.note_end_mod = trk->note_cap ? trk->note_end % trk->note_cap : 0;
@@ -361,21 +309,18 @@ extern "C" srt_status srt_tracker_rx(srt_tracker *trk, const uint32_t *d_out_hos
         return SRT_OK;
     }
     if (!c.n_hosts) return SRT_OK;
-    if (hipSetDevice(trk->plan->device) != hipSuccess) return SRT_ERR_HIP;
+    if (!stage::use_device(trk->plan)) return SRT_ERR_HIP;
     hipStream_t s = trk->plan->stream;
-    const bool wide = out_cap > (uint64_t)WIDE_AVG * c.n_hosts;
-    if (wide) hipLaunchKernelGGL(tracker_rx_kernel<64>, dim3(host_blocks(c.n_hosts, true)), dim3(BT), 0, s, c);
-    else hipLaunchKernelGGL(tracker_rx_kernel<8>, dim3(host_blocks(c.n_hosts, false)), dim3(BT), 0, s, c);
-    return launched(err);
+    const bool wide = stage::wide(out_cap, c.n_hosts);
+    stage::launch_grouped(tracker_rx_kernel<64>, tracker_rx_kernel<8>, wide, stage::host_blocks(c.n_hosts, wide), BT, s,
+                          c);
+    return stage::launched(err, "tracker");
 }
 
 extern "C" srt_status srt_tracker_rx_flat(srt_tracker *trk, const uint32_t *d_host, const uint32_t *d_socket,
                                           const srt_trk_meta *d_meta, uint64_t n, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!trk || (n && (!d_host || !d_socket || !d_meta))) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!trk || (n && (!d_host || !d_socket || !d_meta))) return stage::null_argument(err);
     if (n >= 0x80000000ull) {
         set_err(err, SRT_ERR_INVALID, "more than 2^31-1 records in one call");
         return SRT_ERR_INVALID;
@@ -390,10 +335,10 @@ extern "C" srt_status srt_tracker_rx_flat(srt_tracker *trk, const uint32_t *d_ho
         tracker::host_rx_flat(c);
         return SRT_OK;
     }
-    if (hipSetDevice(trk->plan->device) != hipSuccess) return SRT_ERR_HIP;
-    hipLaunchKernelGGL(tracker_flat_kernel, dim3((uint32_t)std::min<uint64_t>((n + BT - 1) / BT, LATE_BLOCKS)), dim3(BT),
-                       0, trk->plan->stream, c);
-    return launched(err);
+    if (!stage::use_device(trk->plan)) return SRT_ERR_HIP;
+    hipLaunchKernelGGL(tracker_flat_kernel, dim3(stage::strided_blocks(n, stage::LATE_BLOCKS)), dim3(BT), 0,
+                       trk->plan->stream, c);
+    return stage::launched(err, "tracker");
 }
 
 namespace srt {
@@ -422,7 +367,7 @@ srt_status counters_heartbeat(srt_plan *plan, const char *who, srt_trk_counters 
     srt_trk_counters *dev = recs;
     const bool all = !hosts && !sockets;
     if (plan) {
-        if (hipSetDevice(plan->device) != hipSuccess) return SRT_ERR_HIP;
+        if (!stage::use_device(plan)) return SRT_ERR_HIP;
         hipStream_t s = plan->stream;
         recs = stage;
         if ((rec_bytes && hipMemcpyAsync(recs, dev, rec_bytes, hipMemcpyDeviceToHost, s) != hipSuccess) ||
@@ -470,11 +415,8 @@ extern "C" srt_status srt_tracker_heartbeat(srt_tracker *trk, const uint32_t *ho
                                             srt_trk_counters *out_node_in, srt_trk_counters *out_node_out,
                                             srt_trk_counters *out_sock_in, srt_trk_counters *out_sock_out,
                                             srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!trk) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!trk) return stage::null_argument(err);
     return srt::counters_heartbeat(trk->plan, "tracker", trk->base.node_in, trk->rec_bytes, trk->stage.data(),
                                    trk->n_hosts, trk->n_sockets, hosts, n_sel_hosts, sockets, n_sel_sockets,
                                    out_node_in, out_node_out, out_sock_in, out_sock_out, err);
@@ -482,11 +424,8 @@ extern "C" srt_status srt_tracker_heartbeat(srt_tracker *trk, const uint32_t *ho
 
 extern "C" srt_status srt_tracker_status(srt_tracker *trk, uint32_t *flags, uint64_t *n_tx_counted,
                                          uint64_t *n_rx_counted, srt_err *err) {
-    if (err) std::memset(err, 0, sizeof *err);
-    if (!trk) {
-        set_err(err, SRT_ERR_INVALID, "null argument");
-        return SRT_ERR_INVALID;
-    }
+    stage::begin(err);
+    if (!trk) return stage::null_argument(err);
     tracker::State w;
     if (!trk->plan) {
         const tracker::Ctx &c = trk->base;
@@ -495,16 +434,10 @@ extern "C" srt_status srt_tracker_status(srt_tracker *trk, uint32_t *flags, uint
         w = *c.st;
         c.st->flags = 0;
     } else {
-        if (hipSetDevice(trk->plan->device) != hipSuccess) return SRT_ERR_HIP;
-        hipStream_t s = trk->plan->stream;
-        hipLaunchKernelGGL(tracker_sum_kernel, dim3(1), dim3(ST), 0, s, trk->base);
-        if (hipMemcpyAsync(&w, trk->base.st, sizeof w, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            (void)hipGetLastError();
-            set_err(err, SRT_ERR_HIP, "tracker: stream failed");
-            return SRT_ERR_HIP;
-        }
-        if (w.flags) (void)hipMemsetAsync(&trk->base.st->flags, 0, 4, s);
+        if (!stage::use_device(trk->plan)) return SRT_ERR_HIP;
+        hipLaunchKernelGGL(tracker_sum_kernel, dim3(1), dim3(ST), 0, trk->plan->stream, trk->base);
+        const srt_status st = stage::read_status(trk->plan, &w, trk->base.st, sizeof w, err, "tracker");
+        if (st != SRT_OK) return st;
     }
     const uint32_t f = w.flags & 15u;
     if (flags) *flags = f;

@@ -183,24 +183,16 @@ SRT_HD bool log_get(const Ctx &c, uint64_t seq, srt_trk_meta &m) {
     return true;
 }
 
-// ---- the walks: host h's segment of a grouped array, held below `lim` whatever ptr[] says
-SRT_HD void segment(const uint32_t *ptr, uint32_t lim, uint32_t h, uint32_t &b, uint32_t &e) {
-    b = ptr[h] < lim ? ptr[h] : lim;
-    e = ptr[h + 1] < lim ? ptr[h + 1] : lim;
-    if (e < b) e = b;
-}
+// ---- the walks
+using relay::segment;
 
-SRT_HD uint32_t tx_walked(const Ctx &c) { return c.host_ptr[c.n_hosts] < c.n_pkts ? c.host_ptr[c.n_hosts] : c.n_pkts; }
+SRT_HD uint32_t tx_walked(const Ctx &c) { return relay::walked(c.host_ptr, c.n_hosts, c.n_pkts); }
 
 SRT_HD uint32_t rx_walked(const Ctx &c) {
     return c.out_host_ptr[c.n_hosts] < c.out_cap ? c.out_host_ptr[c.n_hosts] : (uint32_t)c.out_cap;
 }
 
-SRT_HD uint32_t late_n(const Ctx &c) {
-    if (!c.late_count) return 0;
-    const uint32_t n = *c.late_count;
-    return n < c.late_cap ? n : c.late_cap;
-}
+SRT_HD uint32_t late_n(const Ctx &c) { return relay::late_n(c.late_count, c.late_cap); }
 
 // rule 1, and the log for the packets that stay queued
 SRT_HD void tx_batch(const Ctx &c, uint32_t i, Acc &a) {

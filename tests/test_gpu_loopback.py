@@ -15,7 +15,7 @@ import loopback_scenario as S
 
 pytestmark = pytest.mark.gpu
 QDISCS = pytest.mark.parametrize("qdisc", [LM.FIFO, LM.RR], ids=["fifo", "rr"])
-WIDE_AVG, LANES_NARROW, LANES_WIDE, BT = 16, 8, 64, 256  # srt_loopback.hip
+WIDE_AVG, LANES_NARROW, LANES_WIDE, BT = 16, 8, 64, 256  # srt_stage.h (the lane groups: 8 or 64)
 
 
 @pytest.fixture(scope="module")
