@@ -550,6 +550,8 @@ void free_plan_buffers(srt_plan *p) {
     hipFree(p->d_tpk2);
     hipFree(p->d_tsort_tmp);
     hipFree(p->d_tcls);
+    hipFree(p->d_kcls);
+    hipFree(p->d_kcol);
     hipFree(p->d_tcw);
     hipFree(p->d_ev_bad);
     hipFree(p->d_tccnt);
@@ -612,6 +614,7 @@ void read_create_knobs(CreateKnobs &k) {
     read("SRT_LVL_DYN", k.lvl_dyn, as_int);
     read("SRT_LVL_PACK", k.lvl_pack, as_int);
     read("SRT_LVL_CE4", k.lvl_ce4, as_int);
+    read("SRT_LVL_KEEP", k.lvl_keep, as_int);
     read("SRT_LVL_SPREAD", k.lvl_spread, as_int);
     read("SRT_LVL_LEAN", k.lvl_lean, as_int);
     read("SRT_FW_P1", k.fw_p1, as_int);
@@ -992,6 +995,10 @@ srt_status choose_family(Create &c) {
             const size_t at = p->desc.find(" loss=in-solve");
             if (at != std::string::npos) p->desc.insert(at + 14, " ce=4");
         }
+        // the run's class structure, kept from the probe's class rows while they
+        // are at hand (symmetric integer-level plans; knob SRT_LVL_KEEP=0: every
+        // run builds it from the adjacency again)
+        if (!(c.knobs.lvl_keep.set && c.knobs.lvl_keep.v == 0)) ST_TRY(srt::level_keep(p, c.err));
     } else {
         p->lvl_q = 0;
         p->lvl_sym = p->lvl_sym_lat = false;

@@ -373,6 +373,14 @@ struct srt_plan {
     bool lvl_ce4 = false;          // the plan uses them (chosen at create; an overflowing run clears it for good)
     bool lvl_ce4_run = false;      // the last class-CSR build wrote them (level_csr)
     bool lvl_ce4_pending = false;  // ... and its overflow word has not been read yet (srt_plan_sync / srt_plan_fetch)
+    // the kept class structure of a symmetric integer-level plan (level_keep, knob SRT_LVL_KEEP): the run's out-rows
+    // are a prefix of each of the probe's class rows, kept once at creation; a run fills in the losses (level_csr)
+    uint32_t *d_kcls = nullptr;    // 2 * (V * lvl_kstride + 1) class offsets at the run's stride (out, then the same again)
+    uint16_t *d_kcol = nullptr;    // lvl_kept heads, rows by d_kcls
+    uint64_t lvl_kept = 0;         // entries kept (0: no kept structure)
+    uint32_t lvl_kstride = 0;      // class offsets a vertex in d_kcls
+    uint64_t lvl_kbound = 0;       // the bound (units) it was kept at
+    bool lvl_keep_run = false;     // the last class-CSR build filled it (the solve reads d_kcls)
     uint32_t lvl_q = 0, lvl_rb = 0, lvl_vb = 0;  // quantized level solve: bucket width (units), entry field bits
     uint16_t *d_lmem = nullptr;              // its per-workgroup scratch (lmem_cap u16)
     uint64_t lmem_cap = 0;
@@ -558,6 +566,11 @@ struct LevelCtx {
 LevelCtx level_ctx(srt_plan *p);
 // the class CSRs of a level plan at its bound (the run's first step)
 srt_status level_prepare(srt_plan *p, srt_err *err);
+// creation, after the probe proved kp.lmax and while its class rows are still
+// in d_tpk / d_tcls: keeps the run's class structure (d_kcls, d_kcol) of a
+// symmetric integer-level plan, so its runs only fill in the losses; a plan
+// that is not eligible keeps nothing
+srt_status level_keep(srt_plan *p, srt_err *err);
 // rows [r0, r1) staged (row r0 + k at k * n) as u16 (stage_mode 1) or u32 (2)
 // latency units + f32 loss, or as 8-byte records {u32 units, loss bits} (3,
 // quantized plans only); (min latency, unreachable) min/added into d_stats, on

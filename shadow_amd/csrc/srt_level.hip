@@ -414,6 +414,116 @@ __global__ void loss_scatter_kernel(const uint32_t *__restrict__ idx, const floa
         loss[idx[i]] = val[i];
 }
 
+// The kept class structure (level_keep): a plan's graph cannot change after
+// its creation, so which pairs its run lists, in which class and where each
+// list starts is settled once the probe has proved the bound B -- row u of the
+// run's out-rows is the prefix "classes 1..B" of row u of the probe's class
+// rows (lists are stored in class order inside a row).  Kept once at creation:
+// the class offsets at the run's stride (d_kcls) and the heads as u16 columns
+// (d_kcol), rows based by a scan of their kept counts; a run only reads the
+// kept edges' losses and packs the entries (lvl_fill_kernel).
+// Step 1: row u's kept count (cnt[V] = 0, so the scan's last value is the total).
+__global__ void lvl_keep_count_kernel(uint32_t V, uint32_t pcls, uint32_t B, const uint32_t *__restrict__ poff,
+                                      uint32_t *__restrict__ cnt) {
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u > V) return;
+    // slot k of a row: the start of class k + 1 (slot pcls - 1: the row's end; B <= pcls - 1)
+    cnt[u] = u < V ? poff[(uint64_t)u * pcls + B] - poff[(uint64_t)u * pcls] : 0u;
+}
+
+// Step 2, one wave a vertex: the run's class offsets (rcls a vertex, lvl_out_kernel's
+// layout: classes past B empty; written twice, the in-rows being the out-rows)
+// from the probe's (pcls a vertex), and the prefix's heads as u16.
+__global__ __launch_bounds__(256) void lvl_keep_kernel(uint32_t V, uint32_t pcls, uint32_t rcls, uint32_t B,
+                                                       const uint32_t *__restrict__ poff,
+                                                       const uint64_t *__restrict__ pent,
+                                                       const uint32_t *__restrict__ base,
+                                                       uint32_t *__restrict__ koff, uint16_t *__restrict__ kcol) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+    const uint64_t vc1 = (uint64_t)V * rcls + 1;
+    for (uint32_t u = wave; u < V; u += nwaves) {
+        const uint32_t *po = poff + (uint64_t)u * pcls;
+        const uint32_t p0 = po[0], cnt = po[B] - p0, kb = base[u];
+        if (lane < rcls) {
+            const uint32_t o = kb + (lane < B ? po[lane] - p0 : cnt);
+            koff[(uint64_t)u * rcls + lane] = o;
+            koff[vc1 + (uint64_t)u * rcls + lane] = o;
+        }
+        for (uint32_t i = lane; i < cnt; i += 64) kcol[kb + i] = (uint16_t)pent[p0 + i];
+    }
+    if (wave == 0 && lane == 0) {  // the arrays' last word: the total
+        const uint32_t total = base[V];
+        koff[vc1 - 1] = total;
+        koff[2 * vc1 - 1] = total;
+    }
+}
+
+// The run's pass over a kept structure, one wave a row: the kept heads v of row
+// u, their losses gathered (identity rows: loss[row_ptr[u] + v], FILL_UNR x 64
+// of a row in flight: a C3 row's ~330 all go out before the first is used) and
+// the entries stored at the kept indices, the bits lvl_out_kernel's put stores
+// (CE4: 4-byte entries, *ovf set where a difference does not fit).
+constexpr int FILL_UNR = 8;
+template <bool CE4>
+__global__ __launch_bounds__(256) void lvl_fill_kernel(uint32_t V, uint32_t cls, uint32_t vb,
+                                                       const uint64_t *__restrict__ row_ptr,
+                                                       const float *__restrict__ loss,
+                                                       const uint32_t *__restrict__ koff,
+                                                       const uint16_t *__restrict__ kcol, uint64_t *__restrict__ ce_out,
+                                                       unsigned long long *ovf) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+    bool over = false;
+    for (uint32_t u = wave; u < V; u += nwaves) {
+        const uint32_t b = koff[(uint64_t)u * cls], e = koff[(uint64_t)u * cls + cls - 1];
+        const float *lrow = loss + row_ptr[u];
+        for (uint32_t i0 = b + lane; i0 < e; i0 += 64 * FILL_UNR) {
+            uint32_t v[FILL_UNR];
+            float ls[FILL_UNR];
+#pragma unroll
+            for (int r = 0; r < FILL_UNR; ++r) v[r] = i0 + 64 * r < e ? kcol[i0 + 64 * r] : 0u;
+#pragma unroll
+            for (int r = 0; r < FILL_UNR; ++r) ls[r] = i0 + 64 * r < e ? lrow[v[r]] : 0.0f;
+#pragma unroll
+            for (int r = 0; r < FILL_UNR; ++r) {
+                if (i0 + 64 * r >= e) continue;
+                const float eb = 1.0f - ls[r];  // (1f32 - other.packet_loss), mod.rs:328
+                if constexpr (CE4) {
+                    // (a loss outside [0, 1] or a NaN wraps the difference past every field: it overflows too)
+                    const uint32_t d = 0x3f800000u - __float_as_uint(eb);
+                    over |= (d >> (32u - vb)) != 0;
+                    reinterpret_cast<uint32_t *>(ce_out)[i0 + 64 * r] = v[r] | d << vb;
+                } else {
+                    ce_out[i0 + 64 * r] = ((uint64_t)__float_as_uint(eb) << 32) | v[r];
+                }
+            }
+        }
+    }
+    if (CE4 && over) atomicOr(ovf, 1ull);
+}
+
+// the adjacency indices of a kept structure's entries (identity rows), row by
+// row: the one-call build's needed losses without another pass over the latencies
+__global__ __launch_bounds__(256) void lvl_keep_index_kernel(uint32_t V, uint32_t cls,
+                                                             const uint64_t *__restrict__ row_ptr,
+                                                             const uint32_t *__restrict__ koff,
+                                                             const uint16_t *__restrict__ kcol,
+                                                             uint32_t *__restrict__ idx, unsigned long long total,
+                                                             unsigned long long *cnt) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t u = wave; u < V; u += nwaves) {
+        const uint32_t b = koff[(uint64_t)u * cls], e = koff[(uint64_t)u * cls + cls - 1];
+        const uint32_t r = (uint32_t)row_ptr[u];
+        for (uint32_t i = b + lane; i < e; i += 64) idx[i] = r + kcol[i];
+    }
+    if (wave == 0 && lane == 0) *cnt = total;
+}
+
 // ------------------------------------------------------------ level solve
 #if LOSS_COUNT
 __device__ unsigned long long solve_cnt[8];  // diagnostic builds: [1] edge visits, [4] [6] [7] phase ticks: init, levels, out
@@ -440,9 +550,15 @@ static_assert(LIST_T >= 1 && LIST_T * LIST_LPI == PACK_NT, "a listed level's ite
 // The wave walk of the other push-only levels of the packed row (LVL_LEAN_WAVE):
 // WAVE_B: items of a batch, dealt to the waves by a counter; WAVE_D: 64-entry
 // passes in flight; WAVE_U: passes folded together (C3: 8 / 4 3.49 ms the solve,
-// 4 / 2 3.65, 4 / 1 3.79, 12 / 4 3.78; 32 items a batch +0.14).
+// 4 / 2 3.65, 4 / 1 3.79, 12 / 4 3.78; 32 items a batch +0.14).  56 items a
+// batch, not a lane's 64: a batch's passes are read in windows of 64, a lane a
+// pass, and C3's class-1 lists (55 entries on average, one in ten of two
+// passes) make about 70 passes of 64 items -- a second window of a few passes
+// with a ring fill and drain of its own -- and 61.6 of 56, one window nine
+// times in ten (r12, the solve: 64 items 3.389 ms, 60 3.405, 58 3.344, 56 3.299,
+// 54 3.300, 52 3.309, 48 3.339).
 #ifndef SRT_WAVE_B
-#define SRT_WAVE_B 64
+#define SRT_WAVE_B 56
 #endif
 #ifndef SRT_WAVE_D
 #define SRT_WAVE_D 8
@@ -1691,7 +1807,7 @@ LevelCtx level_ctx(srt_plan *p) {
     c.n = p->n;
     c.g = p->kp.g;
     c.t_cls = p->t_cls;
-    c.tcls = p->d_tcls;
+    c.tcls = p->lvl_keep_run ? p->d_kcls : p->d_tcls;  // (a kept structure's offsets: level_keep)
     c.ce_out = p->d_tpk;
     c.ce_in = p->lvl_single ? p->d_tpk : p->d_tpk2;
     c.nodes = p->d_nodes;
@@ -1748,6 +1864,11 @@ int level_rows_per_cu(uint32_t V, bool quant, bool packed) {
 
 namespace {
 // ------------------------------------------------------------ level solve
+// a run of p at its bound fills a kept class structure (level_keep): the plan is still symmetric
+bool level_keep_applies(const srt_plan *p) {
+    return p->lvl_kept && p->lvl_sym && !p->lvl_q && p->lvl_kbound == p->kp.lmax;
+}
+
 // what both class-CSR builds allocate: class offsets and counts, cursor, class max
 srt_status level_csr_arrays(srt_plan *p, uint64_t vc1, srt_err *err) {
     uint64_t cap_cur = p->d_tcursor ? 1 : 0, cap_mw = p->d_tmaxw ? 1 : 0;
@@ -1809,6 +1930,24 @@ srt_status level_csr(srt_plan *p, uint64_t wmax, bool with_loss, srt_err *err, b
     const bool use4 = ce4 && single && with_loss && !q && p->d_lvisit;
     p->lvl_ce4_run = use4;
     const uint32_t vb = q ? p->lvl_vb : use4 ? level_vbits(V) : 32u;
+    // a kept class structure (level_keep): the lists and their offsets stand since
+    // creation, this run's losses are filled into them -- one launch, no pass over
+    // the adjacency, no cursor, no offsets copy.  (4-byte entries: the caller has
+    // zeroed the overflow word, level_run)
+    p->lvl_keep_run = false;
+    if (with_loss && wmax == p->kp.lmax && level_keep_applies(p) && p->lvl_kstride == cls) {
+        cspan_begin(p);
+        hipLaunchKernelGGL(use4 ? lvl_fill_kernel<true> : lvl_fill_kernel<false>, dim3(blocks), dim3(256), 0, M, V, cls, vb,
+                           p->d_row_ptr, p->d_loss, p->d_kcls, p->d_kcol, p->d_tpk,
+                           use4 ? p->d_lvisit + 1 : (unsigned long long *)nullptr);
+        cspan_end(p);
+        p->lvl_keep_run = true;
+        p->t_cls = cls;
+        p->t_q = 1;
+        p->t_level = true;
+        p->t_edges = p->lvl_cap;  // (as the adjacency pass reports it: the probe's count)
+        return SRT_OK;
+    }
     auto out_pass = [&]() {
         if (!single)  // in-row counts, then in-row cursors (out-rows-only plans count none)
             (void)hipMemsetAsync(p->d_tccnt, 0, 2 * vc1 * 4, M);
@@ -1968,6 +2107,7 @@ srt_status level_csr_sharded(srt_plan *p, uint64_t wmax, bool with_loss, uint32_
     cspan_end(p);
     if (e != hipSuccess) return fail(err, e, "class offsets (sharded)");
     p->lvl_single = true;
+    p->lvl_keep_run = false;
     p->lvl_ce4_run = false;  // the slice exchange moves 8-byte entries
     p->t_cls = cls;
     p->t_q = 1;
@@ -2223,6 +2363,58 @@ srt_status level_sharded(srt_plan *p, unsigned long long *d_stats, srt_err *err)
 
 srt_status level_prepare(srt_plan *p, srt_err *err) { return level_csr(p, p->kp.lmax, true, err); }
 
+srt_status level_keep(srt_plan *p, srt_err *err) {
+    static_assert(LEVEL_V_MAX <= 65536, "kept heads are u16");
+    p->lvl_kept = 0;
+    p->lvl_keep_run = false;
+    const uint32_t V = p->V;
+    const uint64_t B = p->kp.lmax;
+    // out-rows only (identity rows, mirrored latencies), exact classes, heads that fit u16,
+    // and the probe's class rows at hand (out-rows only as well: its last build was loss-free)
+    if (!p->lvl_sym_lat || !p->ident_rows || p->lvl_q || V > 65536 || !p->lvl_cap || !p->lvl_single || !p->d_tcls ||
+        !p->d_tpk || !p->d_tccnt)
+        return SRT_OK;
+    const uint32_t pcls = p->t_cls;                            // the probe's offsets a vertex
+    const uint32_t rcls = B < 16 ? 16 : B < 32 ? 32 : 64;      // the run's (level_csr)
+    if (B < 1 || B >= pcls || p->tcls_cap < 2ull * V + 2) return SRT_OK;
+    hipStream_t M = p->stream;
+    const uint64_t vc1 = (uint64_t)V * rcls + 1;
+    uint32_t *cnt = p->d_tccnt, *base = p->d_tccnt + V + 1;  // (the in-row counts: out-rows-only plans count none)
+    srt_status st = scan_scratch(p, (size_t)V + 1, err);
+    if (st != SRT_OK) return st;
+    cspan_begin(p);
+    hipLaunchKernelGGL(lvl_keep_count_kernel, dim3((V + 256) / 256), dim3(256), 0, M, V, pcls, (uint32_t)B, p->d_tcls, cnt);
+    st = exclusive_scan_u32(p, cnt, base, (size_t)V + 1, err);
+    cspan_end(p);
+    if (st != SRT_OK) return st;
+    uint32_t total = 0;
+    hipError_t e = hipMemcpyAsync(&total, base + V, 4, hipMemcpyDeviceToHost, M);
+    if (e == hipSuccess) e = hipStreamSynchronize(M);
+    if (e != hipSuccess) return fail(err, e, "level keep (count)");
+    if (!total || total > p->lvl_cap) return SRT_OK;
+    (void)hipFree(p->d_kcls);
+    (void)hipFree(p->d_kcol);
+    p->d_kcls = nullptr;
+    p->d_kcol = nullptr;
+    uint64_t ca = 0, cb = 0;
+    if ((st = grow(&p->d_kcls, &ca, 2 * vc1, err, "hipMalloc(kept class offsets)")) != SRT_OK ||
+        (st = grow(&p->d_kcol, &cb, (uint64_t)total + 1024, err, "hipMalloc(kept columns)")) != SRT_OK)
+        return st;
+    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(8192, (V + 3) / 4));
+    cspan_begin(p);
+    hipLaunchKernelGGL(lvl_keep_kernel, dim3(blocks), dim3(256), 0, M, V, pcls, rcls, (uint32_t)B, p->d_tcls, p->d_tpk, base,
+                       p->d_kcls, p->d_kcol);
+    cspan_end(p);
+    if ((e = hipGetLastError()) != hipSuccess) return fail(err, e, "level keep");
+    p->lvl_kept = total;
+    p->lvl_kstride = rcls;
+    p->lvl_kbound = B;
+    if (std::getenv("SRT_TRACE"))
+        std::fprintf(stderr, "[srt] level keep: %llu of %llu entries, classes <= %llu\n", (unsigned long long)total,
+                     (unsigned long long)p->lvl_cap, (unsigned long long)B);
+    return SRT_OK;
+}
+
 void level_solve_stage(const LevelCtx &c, uint32_t r0, uint32_t r1, uint32_t lmax, void *stage_lat,
                        float *stage_loss, uint32_t stage_mode, unsigned long long *d_stats) {
     launch_solve_ctx(c, d_stats, nullptr, r0, r1, lmax, false, nullptr, stage_lat, stage_loss, stage_mode);
@@ -2247,6 +2439,11 @@ int level_pack_fit(uint32_t V, bool nt_store, bool ce4) {
 
 void level_loss_index(srt_plan *p, uint32_t *d_idx, uint64_t cap, unsigned long long *d_cnt, hipStream_t s) {
     const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(8192, (p->V + 3) / 4));
+    if (p->lvl_kept && !p->lvl_q && p->lvl_kbound == p->kp.lmax && p->lvl_kept <= cap) {  // the kept structure lists them
+        hipLaunchKernelGGL(lvl_keep_index_kernel, dim3(blocks), dim3(256), 0, s, p->V, p->lvl_kstride, p->d_row_ptr,
+                           p->d_kcls, p->d_kcol, d_idx, (unsigned long long)p->lvl_kept, d_cnt);
+        return;
+    }
     (void)hipMemsetAsync(d_cnt, 0, sizeof *d_cnt, s);
     // identity rows: the column is the entry's place in its row (no column loads)
     hipLaunchKernelGGL(p->ident_rows ? lvl_index_kernel<true> : lvl_index_kernel<false>, dim3(blocks), dim3(256), 0, s,
@@ -2354,6 +2551,7 @@ srt_status level_run(srt_plan *p, unsigned long long *d_stats, srt_err *err) {
     // after an overflow is srt_plan_sync's and srt_plan_fetch's)
     const bool ce4 = p->lvl_ce4 && sym_int && p->lvl_pack && p->lvl_sp && p->kp.lmax <= PACK_LMAX && !p->comm &&
                      !p->fold_chunk_rows;
+    bool zeroed = false;
     if (sym_int && ((p->comm && p->comm->nranks > 1) || (p->row_shard && p->lvl_emu_ranks > 1)))
         level_ce4_off(p);  // the sharded class CSR exchanges 8-byte entries
     if (sym_int && p->comm && p->comm->nranks > 1)
@@ -2362,12 +2560,22 @@ srt_status level_run(srt_plan *p, unsigned long long *d_stats, srt_err *err) {
         st = level_csr_sharded(p, p->kp.lmax, true, p->lvl_emu_ranks,
                                (uint32_t)((uint64_t)p->row0 * p->lvl_emu_ranks / std::max<uint32_t>(p->n, 1)), nullptr,
                                err);
-    else
+    else {
+        // a kept class structure: the run's counters zeroed ahead of the fill, the
+        // 4-byte entries' overflow word with them (nothing else writes the class max)
+        const bool kept = level_keep_applies(p);
+        if (kept)
+            hipLaunchKernelGGL(level_zero_kernel, dim3(1), dim3(1), 0, p->stream, d_stats,
+                               (unsigned long long *)p->d_tmaxw, p->d_lvisit,
+                               ce4 ? p->d_lvisit + 1 : (unsigned long long *)nullptr);
         st = level_csr(p, p->kp.lmax, true, err, ce4);
+        zeroed = kept && st == SRT_OK && p->lvl_keep_run;
+    }
     if (st != SRT_OK) return st;
     p->lvl_ce4_pending = p->lvl_ce4_run;
-    hipLaunchKernelGGL(level_zero_kernel, dim3(1), dim3(1), 0, p->stream, d_stats, (unsigned long long *)p->d_tmaxw,
-                       p->d_lvisit);
+    if (!zeroed)
+        hipLaunchKernelGGL(level_zero_kernel, dim3(1), dim3(1), 0, p->stream, d_stats, (unsigned long long *)p->d_tmaxw,
+                           p->d_lvisit);
 #if LOSS_COUNT
     {
         const uint32_t dg = std::getenv("SRT_LVL_DIAG") ? (uint32_t)std::atoi(std::getenv("SRT_LVL_DIAG")) : 0u;
