@@ -614,6 +614,7 @@ void read_create_knobs(CreateKnobs &k) {
     read("SRT_LVL_DYN", k.lvl_dyn, as_int);
     read("SRT_LVL_PACK", k.lvl_pack, as_int);
     read("SRT_LVL_CE4", k.lvl_ce4, as_int);
+    read("SRT_LVL_CE4_NT", k.lvl_ce4_nt, as_int);
     read("SRT_LVL_KEEP", k.lvl_keep, as_int);
     read("SRT_LVL_SPREAD", k.lvl_spread, as_int);
     read("SRT_LVL_LEAN", k.lvl_lean, as_int);
@@ -989,8 +990,14 @@ srt_status choose_family(Create &c) {
         // SRT_LVL_PACK=1 is the A/B form that knob names, 8-byte entries, unless
         // SRT_LVL_CE4=1 asks too
         const bool want4 = c.knobs.lvl_ce4.set ? c.knobs.lvl_ce4.v != 0 : !c.knobs.lvl_pack.set;
-        p->lvl_ce4 = p->lvl_pack && p->lvl_sym && p->ident_rows && want4 &&
-                     srt::level_pack_fit(p->V, p->lvl_nt, true) >= 2;
+        // ... in workgroups of the widest thread count that still fits twice a CU
+        // (level_ce4_threads; SRT_LVL_CE4_NT forces one of 512 / 640 / 768)
+        if (c.knobs.lvl_ce4_nt.set && !srt::level_ce4_threads_valid((uint32_t)c.knobs.lvl_ce4_nt.v))
+            return refuse(c.err, SRT_ERR_INVALID, "SRT_LVL_CE4_NT must be 512, 640 or 768");
+        p->lvl_ce4_nt = p->lvl_pack && p->lvl_sym && p->ident_rows && want4
+                            ? srt::level_ce4_threads(p->V, p->lvl_nt, c.knobs.lvl_ce4_nt.set ? (uint32_t)c.knobs.lvl_ce4_nt.v : 0u)
+                            : 0u;
+        p->lvl_ce4 = p->lvl_ce4_nt != 0;
         if (p->lvl_ce4) {  // (beside the entries' other field, ahead of the rows' tokens)
             const size_t at = p->desc.find(" loss=in-solve");
             if (at != std::string::npos) p->desc.insert(at + 14, " ce=4");

@@ -34,6 +34,7 @@ struct CreateKnobs {
     Knob<int> lvl_dyn;            // SRT_LVL_DYN: 0 = its rows dealt statically, not by a counter (A/B, tests)
     Knob<int> lvl_pack;           // SRT_LVL_PACK: 0 = never its packed LDS row, 1 = wherever the layout is valid (A/B, tests)
     Knob<int> lvl_ce4;            // SRT_LVL_CE4: 0 = never the packed row's 4-byte class entries, 1 = wherever the packed row runs on a symmetric plan (A/B, tests); unset: with the packed row the plan chose itself (SRT_LVL_PACK unset)
+    Knob<int> lvl_ce4_nt;         // SRT_LVL_CE4_NT: 512, 640 or 768 = the threads of the 4-byte-entry kernel's workgroups (A/B, tests; any other value is refused); unset: the widest that fits twice a CU
     Knob<int> lvl_keep;           // SRT_LVL_KEEP: 0 = every run builds its class rows from the adjacency (A/B, tests); unset or 1 = kept from the probe's wherever eligible (level_keep)
     Knob<int> lvl_spread;        // SRT_LVL_SPREAD: 0 = the packed row's small levels one lane group an item (A/B)
     Knob<int> lvl_lean;           // SRT_LVL_LEAN: 0 = full-row passes around every level's walk (A/B, tests); unset or 1 = the lean

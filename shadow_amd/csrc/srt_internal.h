@@ -373,6 +373,7 @@ struct srt_plan {
     bool lvl_ce4 = false;          // the plan uses them (chosen at create; an overflowing run clears it for good)
     bool lvl_ce4_run = false;      // the last class-CSR build wrote them (level_csr)
     bool lvl_ce4_pending = false;  // ... and its overflow word has not been read yet (srt_plan_sync / srt_plan_fetch)
+    uint32_t lvl_ce4_nt = 0;       // threads of its workgroups: 512, 640 or 768 (level_ce4_threads at create, knob SRT_LVL_CE4_NT)
     // the kept class structure of a symmetric integer-level plan (level_keep, knob SRT_LVL_KEEP): the run's out-rows
     // are a prefix of each of the probe's class rows, kept once at creation; a run fills in the losses (level_csr)
     uint32_t *d_kcls = nullptr;    // 2 * (V * lvl_kstride + 1) class offsets at the run's stride (out, then the same again)
@@ -561,6 +562,7 @@ struct LevelCtx {
     uint32_t pack = 0;                     // packed-row workgroups a CU (srt_plan::lvl_pack; 0: the unpacked row); needs lmem
     bool spread = true;                    // packed row: K lane groups an item in small levels
     bool ce4 = false;                      // packed row: ce_out holds 4-byte entries (srt_plan::lvl_ce4_run)
+    uint32_t ce4_nt = 0;                   // ... walked by workgroups of so many threads (srt_plan::lvl_ce4_nt; 0: PACK_NT)
     uint32_t lean = LVL_LEAN_KEPT;         // the LVL_LEAN_* stages around the walk (srt_plan::lvl_lean)
 };
 LevelCtx level_ctx(srt_plan *p);
@@ -584,7 +586,14 @@ size_t level_scratch_bytes(int device, uint32_t V, bool quant, uint32_t pack = 0
 // packed-row workgroups the runtime keeps resident on a CU of the current
 // device (the kernel's registers and its real dynamic LDS; 0: the query failed)
 int level_rows_per_cu(uint32_t V, bool quant, bool packed);
-int level_pack_fit(uint32_t V, bool nt_store, bool ce4 = false);
+// (ce4: the 4-byte-entry kernel of `threads` a workgroup, 0 = the packed row's 512)
+int level_pack_fit(uint32_t V, bool nt_store, bool ce4 = false, uint32_t threads = 0);
+// the 4-byte-entry kernel's threads a workgroup for a plan of V vertices: the
+// widest of 768 / 640 / 512 of which the runtime keeps two workgroups a CU
+// with the real dynamic LDS (forced != 0: that count, SRT_LVL_CE4_NT); 0 when
+// not even 512 fit twice (no 4-byte entries).  SRT_TRACE prints the choice.
+uint32_t level_ce4_threads(uint32_t V, bool nt_store, uint32_t forced);
+bool level_ce4_threads_valid(uint32_t threads);
 // a level plan leaves the 4-byte class entries for good (a loss did not fit
 // them, or its entries travel between ranks): ` ce=4` leaves its description
 void level_ce4_off(srt_plan *p);

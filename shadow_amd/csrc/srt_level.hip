@@ -545,8 +545,12 @@ __constant__ uint32_t lvl_diag;                // level solve ablations (SRT_LVL
 #define SRT_LIST_T 16
 #endif
 constexpr uint32_t LIST_T = SRT_LIST_T;
-constexpr uint32_t LIST_LPI = PACK_NT / LIST_T;  // lanes an item of a listed level
-static_assert(LIST_T >= 1 && LIST_T * LIST_LPI == PACK_NT, "a listed level's items share the workgroup evenly");
+// (a wider workgroup -- level_ce4_wide_kernel's 640 or 768 threads -- walks a
+// listed level with its first 512 threads, the lanes an item staying 32)
+constexpr uint32_t LIST_NT = 512;                 // threads that walk a listed level
+constexpr uint32_t LIST_LPI = LIST_NT / LIST_T;  // lanes an item of a listed level
+static_assert(LIST_T >= 1 && LIST_T * LIST_LPI == LIST_NT && LIST_NT <= PACK_NT,
+              "a listed level's items share the narrowest workgroup evenly");
 // The wave walk of the other push-only levels of the packed row (LVL_LEAN_WAVE):
 // WAVE_B: items of a batch, dealt to the waves by a counter; WAVE_D: 64-entry
 // passes in flight; WAVE_U: passes folded together (C3: 8 / 4 3.49 ms the solve,
@@ -556,7 +560,11 @@ static_assert(LIST_T >= 1 && LIST_T * LIST_LPI == PACK_NT, "a listed level's ite
 // passes) make about 70 passes of 64 items -- a second window of a few passes
 // with a ring fill and drain of its own -- and 61.6 of 56, one window nine
 // times in ten (r12, the solve: 64 items 3.389 ms, 60 3.405, 58 3.344, 56 3.299,
-// 54 3.300, 52 3.309, 48 3.339).
+// 54 3.300, 52 3.309, 48 3.339).  At 768 threads a workgroup (r13, the solve
+// 2.81 ms) 8 / 4 / 56 stays: 4 / 2 and 48 items the same, 8 / 2 +0.05, 64 items
+// +0.07; a scalar-base entry address +0.04; a min only where the candidate is
+// below the probed key: a region a min +0.01, one region a group of four +0.30,
+// branch-free +1.65 (profiles/r13_level_wide).
 #ifndef SRT_WAVE_B
 #define SRT_WAVE_B 56
 #endif
@@ -897,7 +905,7 @@ __device__ __forceinline__ void level_solve_body(
                 // goes out where the chunk walk's select keeps it.
                 constexpr int D = WAVE_D, U = WAVE_U;
                 const uint32_t Tu = __builtin_amdgcn_readfirstlane(T);
-                const uint32_t per = (Tu + PACK_NT / 64 - 1) / (PACK_NT / 64);
+                const uint32_t per = (Tu + (uint32_t)nw - 1) / (uint32_t)nw;  // (the workgroup's own waves: 8, 10 or 12)
                 const uint32_t bs = per < WAVE_B ? per : WAVE_B;  // a small level: every wave a share
                 for (;;) {
                     uint32_t bi = 0;
@@ -1470,6 +1478,32 @@ __global__ __launch_bounds__(LOSS_NT) void level_ce4_kernel(
                                                         stage16, probe, visit_cnt, idn, row_ctr, mem_all, spread, lean, vb);
 }
 
+// ... in workgroups of NTH = 640 or 768 threads, two a CU as well: 5 or 6 waves
+// a SIMD instead of 4 on the same LDS, which the 4-byte-entry walk's registers
+// allow (78 VGPRs of the 80 that six waves leave; the 8-byte walk's 126 do not)
+// once the chunk walk keeps UNR = 2 entry pairs a lane in flight, not 4.  The
+// wave walk runs at the same rate a wave, so its throughput follows the waves
+// (r13, C3: the solve 3.31 ms at 512 threads, 3.03 at 640, 2.81 at 768).  The
+// body takes its thread and wave counts from blockDim; the plan chooses NTH at
+// its create (level_ce4_threads, knob SRT_LVL_CE4_NT).
+constexpr uint32_t CE4_WIDE_NT[] = {640, 768};  // the wide instantiations' threads (level_ce4_kernel: PACK_NT)
+template <bool NT, int NTH, int UNR>
+__global__ __launch_bounds__(NTH, 2 * NTH / 256) void level_ce4_wide_kernel(
+    uint32_t V, const uint32_t *__restrict__ nodes, uint32_t n, uint32_t row0, uint32_t row1,
+    const uint32_t *__restrict__ cls_out, const uint32_t *__restrict__ cls_in, const uint64_t *__restrict__ ce_out,
+    const uint64_t *__restrict__ ce_in, uint32_t lcap, uint64_t g, const uint64_t *__restrict__ sl_lat,
+    const float *__restrict__ sl_loss, uint64_t *__restrict__ out_lat, float *__restrict__ out_loss,
+    unsigned long long *stats, const uint32_t *__restrict__ row_list, void *__restrict__ out32,
+    float *__restrict__ out32_loss, bool stage16, uint32_t *__restrict__ probe,
+    unsigned long long *__restrict__ visit_cnt, bool idn, unsigned long long *row_ctr, uint16_t *mem_all,
+    bool spread, uint32_t lean, uint32_t vb) {
+    static_assert(NTH % 128 == 0 && NTH > (int)PACK_NT && NTH / 64 <= 16,
+                  "two workgroups fill whole waves a SIMD; 16 reduction slots");
+    level_solve_body<4, UNR, 16, 2, NT, true, true, true>(V, nodes, n, row0, row1, cls_out, cls_in, ce_out, ce_in, lcap, g, sl_lat,
+                                                          sl_loss, out_lat, out_loss, stats, row_list, out32, out32_loss,
+                                                          stage16, probe, visit_cnt, idn, row_ctr, mem_all, spread, lean, vb);
+}
+
 // ------------------------------------------------- quantized level solve
 // The level solve for latencies that are not small integers of g (Shadow
 // reads any unit down to ns, units.rs:377-388: C3ns has g = 1 ns and edges of
@@ -1826,6 +1860,7 @@ LevelCtx level_ctx(srt_plan *p) {
     c.pack = p->lvl_pack;
     c.spread = p->lvl_spread;
     c.ce4 = p->lvl_ce4_run;
+    c.ce4_nt = p->lvl_ce4_nt;
     // (the packed row's listed levels: LIST_T items at most; SRT_LVL_LIST_T: fewer, A/B)
     const char *lt = std::getenv("SRT_LVL_LIST_T");
     const uint32_t list_t = std::min<uint32_t>(lt ? (uint32_t)std::atoi(lt) : LIST_T, LIST_T);
@@ -2121,15 +2156,23 @@ auto pick_packed_kernel(bool nt_store) {
     return nt_store ? level_solve_kernel<4, 4, 16, 2, true, true, true> : level_solve_kernel<4, 4, 16, 2, false, true, true>;
 }
 // ... on 4-byte class entries
-auto pick_ce4_kernel(bool nt_store) { return nt_store ? level_ce4_kernel<true> : level_ce4_kernel<false>; }
+// (threads: PACK_NT, or one of CE4_WIDE_NT with the chunk walk at two entry pairs a lane)
+auto pick_ce4_kernel(bool nt_store, uint32_t threads = PACK_NT) {
+    static_assert(CE4_WIDE_NT[0] == 640 && CE4_WIDE_NT[1] == 768, "the instantiations below");
+    return threads == 768   ? (nt_store ? level_ce4_wide_kernel<true, 768, 2> : level_ce4_wide_kernel<false, 768, 2>)
+           : threads == 640 ? (nt_store ? level_ce4_wide_kernel<true, 640, 2> : level_ce4_wide_kernel<false, 640, 2>)
+                            : (nt_store ? level_ce4_kernel<true> : level_ce4_kernel<false>);
+}
 
 // Workgroups of a level solve launch over `rows` rows (one row per
 // workgroup at a time; the LDS row decides how many fit a CU)
-uint32_t level_grid(int device, uint32_t V, bool quant, uint32_t rows, uint32_t *nt_out, uint32_t pack) {
-    // the packed row: PACK_NT threads a workgroup, `pack` workgroups a CU (what
-    // the runtime said of the kernel's registers and this LDS row at the create)
+uint32_t level_grid(int device, uint32_t V, bool quant, uint32_t rows, uint32_t *nt_out, uint32_t pack,
+                    uint32_t pack_nt = PACK_NT) {
+    // the packed row: PACK_NT threads a workgroup (pack_nt: the 4-byte-entry
+    // kernel's own count), `pack` workgroups a CU (what the runtime said of the
+    // kernel's registers and this LDS row at the create)
     if (pack) {
-        if (nt_out) *nt_out = PACK_NT;
+        if (nt_out) *nt_out = pack_nt;
         return std::max<uint32_t>(1, std::min<uint32_t>(rows, (uint32_t)cu_count(device) * pack));
     }
     // workgroups a CU's LDS holds, then the fewest threads a workgroup (256,
@@ -2187,7 +2230,8 @@ void launch_solve_ctx(const LevelCtx &c, unsigned long long *d_stats, const uint
     // rows' caps are past its 4-bit levels)
     const uint32_t pack = !quant && !probe && c.sp && c.t_cls == 16 && lcap <= PACK_LMAX && c.lmem ? c.pack : 0u;
     uint32_t nt = 0;
-    const uint32_t grid = level_grid(c.device, V, quant, rows, &nt, pack);
+    const uint32_t ce4_nt = pack && c.ce4 && c.ce4_nt ? c.ce4_nt : PACK_NT;  // (the overflow repeat, 8-byte entries: PACK_NT)
+    const uint32_t grid = level_grid(c.device, V, quant, rows, &nt, pack, ce4_nt);
     const size_t lds = solve_lds_bytes(V, quant, pack != 0);
     const uint64_t vc1 = (uint64_t)V * c.t_cls + 1;
     const uint32_t *co = c.tcls, *ci = c.tcls + vc1;
@@ -2207,7 +2251,7 @@ void launch_solve_ctx(const LevelCtx &c, unsigned long long *d_stats, const uint
         return;
     }
     if (pack && c.ce4) {  // (4-byte entries are written only for a run on the packed row: level_run)
-        const auto k4 = pick_ce4_kernel(c.nt_store);
+        const auto k4 = pick_ce4_kernel(c.nt_store, nt);
         (void)hipFuncSetAttribute((const void *)k4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BUDGET - 4096));
         hipLaunchKernelGGL(k4, dim3(grid), dim3(nt), lds, c.stream, V, c.nodes, c.n, list ? 0u : r0, r1, co, ci, eo, ei, lcap,
                            c.g, c.sl_lat, c.sl_loss, c.out_lat, c.out_loss, d_stats, list, stage_mode ? stage : nullptr,
@@ -2424,17 +2468,34 @@ size_t level_scratch_bytes(int device, uint32_t V, bool quant, uint32_t pack) {
     return quant || pack ? (size_t)level_grid(device, V, quant, ~0u, nullptr, quant ? 0u : pack) * V * 2 : 0;
 }
 
-int level_pack_fit(uint32_t V, bool nt_store, bool ce4) {
-    const void *kern = ce4 ? (const void *)pick_ce4_kernel(nt_store) : (const void *)pick_packed_kernel(nt_store);
+int level_pack_fit(uint32_t V, bool nt_store, bool ce4, uint32_t threads) {
+    if (!threads || !ce4) threads = PACK_NT;
+    const void *kern = ce4 ? (const void *)pick_ce4_kernel(nt_store, threads) : (const void *)pick_packed_kernel(nt_store);
     int wgs = 0;
     if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BUDGET - 4096)) !=
             hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, kern, (int)PACK_NT, solve_lds_bytes(V, false, true)) !=
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, kern, (int)threads, solve_lds_bytes(V, false, true)) !=
             hipSuccess) {
         (void)hipGetLastError();
         return 0;
     }
     return wgs;
+}
+
+bool level_ce4_threads_valid(uint32_t threads) {
+    return threads == PACK_NT || threads == CE4_WIDE_NT[0] || threads == CE4_WIDE_NT[1];
+}
+
+uint32_t level_ce4_threads(uint32_t V, bool nt_store, uint32_t forced) {
+    const int fit512 = level_pack_fit(V, nt_store, true, PACK_NT);
+    if (fit512 < 2) return 0;
+    const int fit640 = level_pack_fit(V, nt_store, true, CE4_WIDE_NT[0]), fit768 = level_pack_fit(V, nt_store, true, CE4_WIDE_NT[1]);
+    const uint32_t widest = fit768 >= 2 ? CE4_WIDE_NT[1] : fit640 >= 2 ? CE4_WIDE_NT[0] : PACK_NT;
+    const uint32_t threads = forced ? forced : widest;
+    if (std::getenv("SRT_TRACE"))
+        std::fprintf(stderr, "[srt] level ce4: %u threads a workgroup%s (workgroups a CU: 768 x%d, 640 x%d, 512 x%d)\n", threads,
+                     forced ? " (forced)" : "", fit768, fit640, fit512);
+    return threads;
 }
 
 void level_loss_index(srt_plan *p, uint32_t *d_idx, uint64_t cap, unsigned long long *d_cnt, hipStream_t s) {
