@@ -247,7 +247,8 @@ typedef struct {
 /* PacketDeliveryStatusFlags (src/main/routing/packet.minimal.h:24-36): the send
  * decision's two, the inbound router stage's five, the interface's one
  * (PDS_SND_INTERFACE_SENT, packet.minimal.h:21) of the outbound relay stage
- * and its two of the receive stage (packet.minimal.h:27-28) */
+ * and its two of the receive stage (packet.minimal.h:27-28), the UDP socket's
+ * three of srt_udprecv */
 enum {
     SRT_PDS_NONE = 0,
     SRT_PDS_SND_INTERFACE_SENT = 1u << 7,
@@ -258,6 +259,9 @@ enum {
     SRT_PDS_ROUTER_DROPPED = 1u << 12,
     SRT_PDS_RCV_INTERFACE_RECEIVED = 1u << 13,
     SRT_PDS_RCV_INTERFACE_DROPPED = 1u << 14,
+    SRT_PDS_RCV_SOCKET_PROCESSED = 1u << 15, /* the UDP receive stage's three (packet.minimal.h:29-32) */
+    SRT_PDS_RCV_SOCKET_DROPPED = 1u << 16,
+    SRT_PDS_RCV_SOCKET_BUFFERED = 1u << 18,
     SRT_PDS_RELAY_CACHED = 1u << 21,
     SRT_PDS_RELAY_FORWARDED = 1u << 22
 };
@@ -419,9 +423,9 @@ void srt_flight_destroy(srt_flight *fl);
  * times, the packet sizes and each host's download bandwidth.
  * OUT OF SCOPE: the CPU-delay model that reschedules events (host.rs:820-848),
  * the loopback relay (is_local is always false here; the outbound relay is the
- * srt_outbound stage below), and what the socket does with the packet: the
+ * srt_outbound stage below), and what a TCP socket does with the packet: the
  * interface's receive side up to the socket hand-off is the srt_deliver stage
- * below.
+ * below, a UDP socket's receive buffer and reads the srt_udprecv stage.
  * ABI: additive to version 4; detect the stage by its symbols. */
 typedef struct srt_inbound srt_inbound;
 
@@ -544,9 +548,11 @@ void srt_inbound_destroy(srt_inbound *ib);
  * close, say); a caller that disassociates a socket mid-window must treat the
  * window's later deliveries to that socket as the lookup would, or split the
  * window there.
- * OUT OF SCOPE: what the socket does with the packet, the loopback relay, the
- * CPU-delay model.  (The tracker's byte counts of the internet interface are
- * the srt_tracker stage below, pcap capture the srt_pcap stage.)
+ * OUT OF SCOPE: what a TCP socket does with the packet, the loopback relay,
+ * the CPU-delay model.  (A UDP socket's receive buffer and its reads are the
+ * srt_udprecv stage below, which takes this stage's list as it is; the
+ * tracker's byte counts of the internet interface are the srt_tracker stage,
+ * pcap capture the srt_pcap stage.)
  * ABI: additive to version 4; detect the stage by its symbols. */
 typedef struct srt_deliver srt_deliver;
 
@@ -1357,6 +1363,251 @@ srt_status srt_pcap_append_files(srt_pcap *pc, const uint64_t *host_off, const u
 /* the write pass's tile, in bytes: a workgroup assembles and stores that much of d_out at a time */
 uint32_t srt_pcap_tile_bytes(void);
 void srt_pcap_destroy(srt_pcap *pc);
+
+/* ------------------------------------------------ UDP socket receive stage */
+/* What a UDP socket does with the packets srt_deliver_run handed it, and what
+ * the window's recvmsg calls get back, batched over socket slots:
+ * UdpSocket::push_in_packet (host/descriptor/socket/inet/udp.rs:108-168),
+ * recvmsg (:477-572), MessageBuffer (:1056-1134) and the SO_RCVBUF rule
+ * (:900-925).  A socket's state is a FIFO of messages with a byte soft limit,
+ * an optional connected peer, the receive time of the last message read, and
+ * at most one blocked read.  The stage is exact, state included, and has no
+ * feedback into the network.
+ * The events of one socket in the window [previous until_ns, until_ns) run in
+ * time order:
+ *   push   a delivery record whose socket is this slot and whose status has
+ *          RCV_INTERFACE_RECEIVED, at its forward_ns, in list order.  It gets
+ *          RCV_SOCKET_PROCESSED; with a peer set and a source (ip, port) that
+ *          differs from it, RCV_SOCKET_DROPPED; else if !(len_bytes <
+ *          soft_limit), RCV_SOCKET_DROPPED; else the message {tag, recv_ns =
+ *          forward_ns, payload_size, source, user} is appended, len_bytes +=
+ *          payload_size, and it gets RCV_SOCKET_BUFFERED.  The limit is soft:
+ *          a packet arriving one byte below it is accepted whole; a zero-length
+ *          payload is buffered without changing len_bytes.  UDP never sets
+ *          RCV_SOCKET_DELIVERED in the reference, nor does the stage.
+ *   read   srt_udp_read at time_ns: an empty buffer answers -EWOULDBLOCK
+ *          unless SRT_UDP_WAIT is set; otherwise the front message is taken
+ *          (popped unless SRT_UDP_PEEK), copied = min(len, size), return_val =
+ *          SRT_UDP_TRUNC ? size : copied, msg_flags has SRT_UDP_MSG_TRUNC iff
+ *          copied < size, and the socket's last_read_recv_ns becomes the
+ *          message's recv_ns, for peeks too (udp.rs:537-538).
+ *   WAIT   the blocked syscall the reference re-runs when the socket turns
+ *          READABLE (udp.rs:550-568): a WAIT read that finds the buffer empty is
+ *          ARMED.  It completes at the first instant t at which a message is
+ *          buffered, after every push of that socket with forward_ns == t (all
+ *          packets of one relay forward task are pushed inside that task; the
+ *          woken process runs in a later event of the same instant) and before
+ *          the list's own reads of time t.  An armed read survives the call;
+ *          its result is reported by the call that completes it: the arming
+ *          call in d_results[r] with complete_ns = t, a later call as a record
+ *          {read seq, result} appended to d_late.  One armed read a socket: a
+ *          second WAIT read that finds the buffer empty meanwhile is flagged
+ *          ARMED_TWICE and answered -EWOULDBLOCK.
+ * At equal times pushes run before reads.
+ * LIMIT: the reference orders a running process's syscall and a forward task of
+ * the same instant by event id, which the library does not own.  A caller who
+ * knows a read preceded a push of the same nanosecond splits the window there.
+ * LIMIT: a host's loopback deliveries (srt_loopback) are not merged into the
+ * same window here; a socket that receives on both interfaces in one window is
+ * the caller's to order.
+ * A record whose socket is UINT32_MAX, a placeholder record (no
+ * RCV_INTERFACE_RECEIVED), a record whose slot is not open here (a TCP socket,
+ * say: FOREIGN to this stage) and a record listed under a host that does not own
+ * its slot pass through: d_rx_status[k] is deliver's status unchanged.
+ * OUT OF SCOPE: TCP sockets and legacy_tcp, the send buffer, shutdown(2), the
+ * CPU-delay model, the tracker's socket-buffer line (tcp.c only).
+ * ABI: additive to version 4; detect the stage by its symbols. */
+typedef struct srt_udprecv srt_udprecv;
+
+/* what the socket needs from a packet, 16 bytes; `user` is opaque and comes back with the message */
+typedef struct {
+    uint32_t src_ip_be;
+    uint16_t src_port_be;
+    uint16_t reserved;
+    uint32_t payload_size;
+    uint32_t user;
+} srt_udp_meta;
+
+#define SRT_UDP_PEEK  0x2u     /* srt_udp_read.flags: MSG_PEEK */
+#define SRT_UDP_TRUNC 0x20u    /* MSG_TRUNC: return the message's size, not the bytes copied */
+#define SRT_UDP_WAIT  0x10000u /* a blocking call: neither MSG_DONTWAIT nor O_NONBLOCK */
+#define SRT_UDP_MSG_TRUNC 0x20u /* srt_udp_result.msg_flags: MSG_TRUNC */
+
+/* one recvmsg call, 24 bytes */
+typedef struct {
+    uint64_t time_ns;
+    uint32_t slot;
+    uint32_t len;   /* the sum of the iovecs' lengths */
+    uint32_t flags; /* SRT_UDP_PEEK | SRT_UDP_TRUNC | SRT_UDP_WAIT */
+    uint32_t user;  /* opaque, comes back as read_user */
+} srt_udp_read;
+
+#define SRT_UDP_NOT_TAKEN 0u /* srt_udp_result.status: the read was not run (READ_ORDER, or past the reads' bounds) */
+#define SRT_UDP_DONE      1u /* return_val and the rest are the call's result */
+#define SRT_UDP_ARMED     2u /* blocked: a later call reports it in d_late */
+
+/* what one read returned, 56 bytes */
+typedef struct {
+    uint64_t tag;         /* the message's flight tag */
+    uint64_t recv_ns;     /* when the interface received it (MessageRecvHeader.recv_time) */
+    uint64_t complete_ns; /* when the call returned: its time_ns, or t for a read that blocked */
+    int64_t return_val;   /* bytes, or -EWOULDBLOCK (-11), or -EBADF (-9) */
+    uint32_t status;      /* SRT_UDP_NOT_TAKEN / DONE / ARMED */
+    uint32_t msg_flags;   /* SRT_UDP_MSG_TRUNC or 0 */
+    uint32_t src_ip_be;   /* the message's source: recvmsg's addr */
+    uint16_t src_port_be;
+    uint16_t reserved;
+    uint32_t user;        /* the message's srt_udp_meta.user */
+    uint32_t read_user;   /* the read's srt_udp_read.user */
+} srt_udp_result;
+
+/* an armed read of an EARLIER call that completed in this one, 64 bytes */
+typedef struct {
+    uint64_t seq; /* its call's read_seq_base + its index */
+    srt_udp_result result;
+} srt_udp_late;
+
+#define SRT_UDPRECV_OPEN       1u /* value: recv_buf_size, the soft limit as given (UdpSocket::new, udp.rs:60-68) */
+#define SRT_UDPRECV_CLOSE      2u /* drops what is buffered, disarms a waiting read */
+#define SRT_UDPRECV_SET_PEER   3u /* connect: value = ip_be | (uint64_t)port_be << 32; 0 clears the peer */
+#define SRT_UDPRECV_SET_RCVBUF 4u /* value: optval; the limit becomes min(max(optval * 2, 2048), 2^28) (udp.rs:910-924) */
+
+/* one configuration step of a socket slot, 16 bytes */
+typedef struct {
+    uint32_t op;
+    uint32_t slot;
+    uint64_t value;
+} srt_udprecv_op;
+
+#define SRT_UDPRECV_RING_OVERFLOW 1u  /* a socket held more than ring_cap messages at the end of a call */
+#define SRT_UDPRECV_LATE_OVERFLOW 2u  /* more late records than late_cap */
+#define SRT_UDPRECV_NOTE_OVERRUN  4u  /* a tag the note ring does not hold: the record is skipped */
+#define SRT_UDPRECV_BAD_SOCKET    8u  /* a read's slot is >= n_sockets, not its host's, or not open: -EBADF */
+#define SRT_UDPRECV_READ_ORDER    16u /* a read outside the window or decreasing within its host: not taken */
+#define SRT_UDPRECV_ARMED_TWICE   32u /* a WAIT read while the socket has an armed one: -EWOULDBLOCK */
+
+#define SRT_UDPRECV_MARK_RING 1u /* srt_udprecv_socket_state.overflow bits */
+#define SRT_UDPRECV_MARK_NOTE 2u
+
+/* a socket slot's state, 48 bytes; UINT64_MAX: none */
+typedef struct {
+    uint64_t len_bytes;
+    uint64_t soft_limit;
+    uint64_t last_read_recv_ns; /* recv_time_of_last_read_packet */
+    uint64_t armed_seq;         /* the blocked read's sequence number */
+    uint32_t n_msgs;
+    uint32_t peer_ip_be;
+    uint16_t peer_port_be;
+    uint8_t open;
+    uint8_t overflow; /* SRT_UDPRECV_MARK_*: the slot's results are invalid since */
+    uint32_t reserved;
+} srt_udprecv_socket_state;
+
+/* An instance for n_hosts hosts on the plan's device and stream, or, with plan
+ * == NULL, host-only: every array argument named d_ is then a HOST pointer and
+ * the calls complete before they return.  Both forms run the same step and
+ * agree byte for byte.  Host h owns the global socket slots [socket_ptr[h],
+ * socket_ptr[h + 1]) (HOST pointer, n_hosts + 1 entries, copied; socket_ptr[0]
+ * == 0, nondecreasing, else SRT_ERR_INVALID); they are the slots srt_tracker
+ * uses: a caller names its associations by slot, so srt_deliver_run's
+ * d_out_socket is the slot.  n_sockets = socket_ptr[n_hosts] and n_hosts are
+ * below 2^31.  ring_cap (below 2^31) is the number of messages a socket may
+ * hold buffered ACROSS calls; inside a call a socket's queue is as long as the
+ * call's list makes it.  note_cap is at most 2^31.  late_cap_hint, the largest
+ * late_cap the caller means to pass, is checked (below 2^31) and sizes nothing
+ * yet.  Memory of the instance, in bytes:
+ *   round16(48 + n_sockets * 88) + n_sockets * ring_cap * 32 + note_cap * 16
+ *      + max(n_sockets, 1024) * 16 + 16 + out_cap * 32
+ * (the state words and the late count of a caller that passes none, 48, and
+ * per slot its 88-byte state record, together rounded up to a multiple of 16;
+ * per slot its ring of messages; the note ring of srt_udp_meta; the
+ * configuration steps of one launch; 16 spare bytes; a 32-byte staged record
+ * per delivery record of the largest out_cap seen), on the device.  The
+ * staged records are the one thing that grows: the first run, and a run with a
+ * larger out_cap than any before,
+ * wait for the stream and reallocate them; no other run allocates or waits.
+ * Destroy the instance before its plan. */
+srt_status srt_udprecv_create(srt_plan *plan, uint32_t n_hosts, const uint32_t *socket_ptr, uint32_t ring_cap,
+                              uint64_t note_cap, uint32_t late_cap_hint, srt_udprecv **out, srt_err *err);
+
+/* Socket configuration between runs: n steps (HOST pointer), applied in list
+ * order, one launch on the plan's stream for every n_sockets (at least 1024)
+ * steps.  EVERY call first waits for the stream's earlier work (the instance
+ * keeps one sorted copy of the steps on the host), so batch a window's steps
+ * into one call.  A slot >= n_sockets or an unknown op returns SRT_ERR_INVALID
+ * and changes NOTHING.  OPEN gives an empty buffer, len_bytes 0, no peer, no last
+ * read time, no mark; on an open slot it does the same.  Every other step on a
+ * slot that is not open is ignored.  A limit set below the current len_bytes
+ * leaves has_space() false until reads drain the buffer. */
+srt_status srt_udprecv_config(srt_udprecv *ur, const srt_udprecv_op *ops, uint64_t n, srt_err *err);
+
+/* srt_deliver_note's and srt_tracker_note's contract for srt_udp_meta: after a
+ * round's srt_flight_push with d_tag == NULL, d_meta[i] for batch packet i,
+ * whose tag is tag_base + i, goes into the instance's ring at tag % note_cap.
+ * tag_base must not lie below the previous note's end (SRT_ERR_INVALID).  A tag
+ * is readable iff tag < note_end && note_end - tag <= note_cap.  n_pkts < 2^31.
+ * Asynchronous on the plan's stream. */
+srt_status srt_udprecv_note(srt_udprecv *ur, const srt_udp_meta *d_meta, uint64_t n_pkts, uint64_t tag_base,
+                            srt_err *err);
+
+/* One call per srt_deliver_run call, in order, on that call's outputs as they
+ * are: the walk over the delivery list is bounded on the device by
+ * min(d_out_host_ptr[n_hosts], out_cap), so nothing is read back between the
+ * two stages.  The window's reads are grouped by host through d_read_host_ptr
+ * (n_hosts + 1 entries; may be NULL when n_reads == 0), within a host in issue
+ * order with nondecreasing time_ns; n_reads (< 2^31) may be the list's
+ * capacity, the walk is bounded by min(d_read_host_ptr[n_hosts], n_reads).  A
+ * read's sequence number is *read_seq_base + its index (read_seq_base, host
+ * pointer, may be NULL: the running count of all earlier calls' n_reads).
+ * until_ns must not lie below the previous call's (SRT_ERR_INVALID).
+ * PRECONDITION: d_out_host_ptr and d_read_host_ptr start at 0 and are
+ * nondecreasing, as srt_deliver_run emits the first.  With pointers that
+ * decrease every access still stays inside the arrays, but which records and
+ * reads a slot sees is then unspecified and the device and host-only forms
+ * need not agree; nothing flags it.
+ * Outputs: d_rx_status[k] for every walked record k, deliver's status OR the
+ * socket's bits; d_results[r] for every r < n_reads; d_late (late_cap records,
+ * any order) and *d_late_count (written by the call; beyond late_cap:
+ * LATE_OVERFLOW); d_first_readable_ns[slot] for every slot: the time of the
+ * socket's first empty -> non-empty transition in this call, else UINT64_MAX
+ * (what wakes poll / epoll waiters).
+ * Conditions, collected for srt_udprecv_status; every write is range-checked
+ * first, a flagged call never writes out of bounds:
+ *   RING_OVERFLOW  the newest messages beyond ring_cap are lost, the socket is
+ *                  marked in its state and only its results are invalid;
+ *   LATE_OVERFLOW  the records beyond late_cap are lost;
+ *   NOTE_OVERRUN   the record is skipped (status unchanged), the socket marked;
+ *   BAD_SOCKET     the read is answered -EBADF, whatever its time;
+ *   READ_ORDER     a read below the previous until_ns, at or after until_ns,
+ *                  or below an earlier read of its host's list that lies in the
+ *                  window: not taken, status SRT_UDP_NOT_TAKEN;
+ *   ARMED_TWICE    answered -EWOULDBLOCK.
+ * Asynchronous on the plan's stream, two launches: it does not wait for the
+ * device, except where the staged records grow (srt_udprecv_create). */
+srt_status srt_udprecv_run(srt_udprecv *ur, const uint32_t *d_out_host_ptr, const uint32_t *d_out_socket,
+                           const uint64_t *d_out_forward_ns, const uint64_t *d_out_tag, const uint32_t *d_out_status,
+                           uint64_t out_cap, const uint32_t *d_read_host_ptr, const srt_udp_read *d_reads,
+                           uint64_t n_reads, uint64_t *read_seq_base, uint64_t until_ns, uint32_t *d_rx_status,
+                           srt_udp_result *d_results, srt_udp_late *d_late, uint32_t late_cap, uint32_t *d_late_count,
+                           uint64_t *d_first_readable_ns, srt_err *err);
+
+/* Synchronises the stream and sums the sockets' counts with one launch.
+ * *flags (may be NULL): the SRT_UDPRECV_* conditions met since the last status
+ * call (then cleared); *n_processed / *n_buffered / *n_dropped (may be NULL):
+ * packets the sockets processed, buffered and dropped since create.
+ * SRT_ERR_INVALID, with a message that names every flag set, when any was;
+ * else SRT_OK. */
+srt_status srt_udprecv_status(srt_udprecv *ur, uint32_t *flags, uint64_t *n_processed, uint64_t *n_buffered,
+                              uint64_t *n_dropped, srt_err *err);
+
+/* Synchronises and copies every slot's state to out[n_sockets] (HOST pointer). */
+srt_status srt_udprecv_state(srt_udprecv *ur, srt_udprecv_socket_state *out, srt_err *err);
+
+/* the bytes of delivery records (32 each, staged) and reads (24 each) a wave of 64 slots holds in LDS:
+ * its hosts' records if they fit, their reads if they fit what is left; a list that does not fit is
+ * walked in device memory instead */
+uint32_t srt_udprecv_window_bytes(void);
+void srt_udprecv_destroy(srt_udprecv *ur);
 
 /* ---------------------------------------------------- IP assignment (a10) */
 /* IpAssignment<u32> (src/main/network/graph/mod.rs:352-420): IPv4 address ->

@@ -51,6 +51,16 @@ LOOPBACK_TIME_ORDER, LOOPBACK_BAD_SOCKET, LOOPBACK_BAD_SLOT = 1, 2, 4
 # srt_pcap_create flags, srt_pcap_status flags
 PCAP_RX_FIRST, PCAP_TX_FIRST = 0, 1
 PCAP_OVERFLOW, PCAP_BAD_PROTOCOL, PCAP_BAD_LENGTH, PCAP_BAD_PAYLOAD, PCAP_TIME_ORDER = 1, 2, 4, 8, 16
+# the UDP socket's packet status bits, srt_udp_read flags, srt_udp_result status and msg_flags,
+# srt_udprecv_op ops, srt_udprecv_status flags, srt_udprecv_socket_state.overflow marks
+PDS_RCV_SOCKET_PROCESSED, PDS_RCV_SOCKET_DROPPED, PDS_RCV_SOCKET_BUFFERED = 1 << 15, 1 << 16, 1 << 18
+UDP_PEEK, UDP_TRUNC, UDP_WAIT = 0x2, 0x20, 0x10000
+UDP_NOT_TAKEN, UDP_DONE, UDP_ARMED = 0, 1, 2
+UDP_MSG_TRUNC = 0x20
+UDPRECV_OPEN, UDPRECV_CLOSE, UDPRECV_SET_PEER, UDPRECV_SET_RCVBUF = 1, 2, 3, 4
+UDPRECV_RING_OVERFLOW, UDPRECV_LATE_OVERFLOW, UDPRECV_NOTE_OVERRUN, UDPRECV_BAD_SOCKET = 1, 2, 4, 8
+UDPRECV_READ_ORDER, UDPRECV_ARMED_TWICE = 16, 32
+UDPRECV_MARK_RING, UDPRECV_MARK_NOTE = 1, 2
 
 
 class SrtErr(C.Structure):
@@ -228,6 +238,15 @@ SIGNATURES = {
     "srt_pcap_append_files": (C.c_int, [_vp, _vp, _vp, _errp]),
     "srt_pcap_tile_bytes": (C.c_uint32, []),
     "srt_pcap_destroy": (None, [_vp]),
+    "srt_udprecv_create": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(_vp), _errp]),
+    "srt_udprecv_config": (C.c_int, [_vp, _vp, C.c_uint64, _errp]),
+    "srt_udprecv_note": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _errp]),
+    "srt_udprecv_run": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _u64p, C.c_uint64,
+                                  _vp, _vp, _vp, C.c_uint32, _vp, _vp, _errp]),
+    "srt_udprecv_status": (C.c_int, [_vp, _u32p, _u64p, _u64p, _u64p, _errp]),
+    "srt_udprecv_state": (C.c_int, [_vp, _vp, _errp]),
+    "srt_udprecv_window_bytes": (C.c_uint32, []),
+    "srt_udprecv_destroy": (None, [_vp]),
     "srt_routing_info_build": (C.c_int, [C.POINTER(SrtCsr), _u32p, C.c_uint32, C.c_int, C.POINTER(SrtOpts),
                                          C.POINTER(_vp), _errp]),
     "srt_routing_info_from_plan": (C.c_int, [_vp, C.POINTER(_vp), _errp]),

@@ -3097,6 +3097,7 @@ hipError_t preload_kernels() {
     if (e == hipSuccess) e = preload_tracker();
     if (e == hipSuccess) e = preload_loopback();
     if (e == hipSuccess) e = preload_pcap();
+    if (e == hipSuccess) e = preload_udprecv();
     return e;
 }
 

@@ -1170,6 +1170,139 @@ class LoopbackRelay:
             pass
 
 
+UDP_META_DTYPE = np.dtype([("src_ip_be", "<u4"), ("src_port_be", "<u2"), ("reserved", "<u2"), ("payload_size", "<u4"),
+                           ("user", "<u4")])
+UDP_READ_DTYPE = np.dtype([("time_ns", "<u8"), ("slot", "<u4"), ("len", "<u4"), ("flags", "<u4"), ("user", "<u4")])
+UDP_RESULT_DTYPE = np.dtype([("tag", "<u8"), ("recv_ns", "<u8"), ("complete_ns", "<u8"), ("return_val", "<i8"),
+                             ("status", "<u4"), ("msg_flags", "<u4"), ("src_ip_be", "<u4"), ("src_port_be", "<u2"),
+                             ("reserved", "<u2"), ("user", "<u4"), ("read_user", "<u4")])
+UDP_LATE_DTYPE = np.dtype([("seq", "<u8"), ("result", UDP_RESULT_DTYPE)])
+UDP_OP_DTYPE = np.dtype([("op", "<u4"), ("slot", "<u4"), ("value", "<u8")])
+UDP_STATE_DTYPE = np.dtype([("len_bytes", "<u8"), ("soft_limit", "<u8"), ("last_read_recv_ns", "<u8"),
+                            ("armed_seq", "<u8"), ("n_msgs", "<u4"), ("peer_ip_be", "<u4"), ("peer_port_be", "<u2"),
+                            ("open", "u1"), ("overflow", "u1"), ("reserved", "<u4")])
+
+
+class UdpReceive:
+    """srt_udprecv: the UDP sockets' receive buffers and reads behind
+    DeliverStage.run (UdpSocket::push_in_packet, recvmsg, MessageBuffer, the
+    SO_RCVBUF rule), a socket slot a lane.  socket_ptr [n_hosts+1] gives every
+    host its global slots, the ones Tracker uses.  config() opens, closes,
+    connects and resizes sockets (UDP_OP_DTYPE, on the host); note() stores a
+    round's UDP_META_DTYPE records under the flight tags of the round's push;
+    run() pushes one DeliverStage.run list into the sockets and answers the
+    window's reads (UDP_READ_DTYPE -> UDP_RESULT_DTYPE, UDP_LATE_DTYPE).
+
+    Bound to a RoutingPlan (arrays are torch CUDA tensors of its device, the
+    calls are asynchronous on its stream; closing the plan closes it), or
+    host-only with plan=None (arrays are numpy arrays, the same step on the
+    CPU)."""
+
+    def __init__(self, plan: Optional[RoutingPlan], socket_ptr, ring_cap: int, note_cap: int, late_cap_hint: int = 0):
+        self.plan = plan
+        sp = np.ascontiguousarray(socket_ptr, np.uint32).reshape(-1)
+        if len(sp) < 1:
+            raise ValueError("UdpReceive: socket_ptr needs n_hosts + 1 entries")
+        self.n_hosts, self.n_sockets = len(sp) - 1, int(sp[-1])
+        self._h = C.c_void_p()
+        if plan is not None:
+            _bind_to_plan(self, plan)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_udprecv_create(plan.handle if plan is not None else None, self.n_hosts,
+                                                 sp.ctypes.data, int(ring_cap), int(note_cap), int(late_cap_hint),
+                                                 C.byref(self._h), C.byref(err)), err)
+
+    _ptr = staticmethod(InboundRouter._ptr)
+    _nbytes = staticmethod(SendBatch._nbytes)
+    _streams = FlightStore._streams
+
+    @staticmethod
+    def window_bytes() -> int:
+        """srt_udprecv_window_bytes: the bytes of staged delivery records (32
+        each) and reads (24 each) a wave holds in LDS"""
+        return int(_lib.lib().srt_udprecv_window_bytes())
+
+    def config(self, ops):
+        """srt_udprecv_config: UDP_OP_DTYPE records (a host numpy array), applied in
+        list order.  Raises SrtError, and changes nothing, for a bad slot or op."""
+        a = np.ascontiguousarray(ops, UDP_OP_DTYPE).reshape(-1)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_udprecv_config(self._h, a.ctypes.data if len(a) else None, len(a), C.byref(err)), err)
+
+    def note(self, meta, tag_base: int):
+        """srt_udprecv_note after FlightStore.push (tag=None) of a round: meta, a
+        uint8 view of the round's 16-byte srt_udp_meta records, one a batch
+        packet; tag_base as the push returned it."""
+        n_pkts = self._nbytes(meta) // 16
+        cur, ps = self._streams(meta) if n_pkts else (None, None)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_udprecv_note(self._h, self._ptr(meta), n_pkts, int(tag_base), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)
+
+    def run(self, out_host_ptr, out_socket, out_forward_ns, out_tag, out_status, read_host_ptr, reads, until_ns: int,
+            rx_status, results, late, late_count, first_readable_ns) -> int:
+        """srt_udprecv_run on DeliverStage.run's outputs as they are: out_host_ptr
+        int32/uint32 [n_hosts+1], out_socket int32/uint32 (its size is
+        out_cap), out_forward_ns and out_tag int64/uint64, out_status
+        int32/uint32, [out_cap] each.  read_host_ptr int32/uint32 [n_hosts+1]
+        and reads, a uint8 view of 24-byte srt_udp_read records (both None: no
+        reads).  Outputs: rx_status int32/uint32 [out_cap]; results, a uint8
+        buffer of 56-byte srt_udp_result records, one a read; late, a uint8
+        buffer of 64-byte srt_udp_late records with late_count a 1-element
+        int32/uint32; first_readable_ns int64/uint64 [n_sockets].  Returns the
+        reads' sequence base.  Device form: enqueue only (status() synchronises)."""
+        out_cap = self._nbytes(out_socket) // 4
+        n_reads = self._nbytes(reads) // 24
+        late_cap = self._nbytes(late) // 64
+        if self._nbytes(out_host_ptr) < 4 * (self.n_hosts + 1) or self._nbytes(out_forward_ns) < 8 * out_cap or \
+                self._nbytes(out_tag) < 8 * out_cap or self._nbytes(out_status) < 4 * out_cap or \
+                self._nbytes(rx_status) < 4 * out_cap or self._nbytes(results) < 56 * n_reads or \
+                (n_reads and self._nbytes(read_host_ptr) < 4 * (self.n_hosts + 1)) or \
+                self._nbytes(first_readable_ns) < 8 * self.n_sockets or (late_cap and late_count is None):
+            raise ValueError("UdpReceive.run: an array is smaller than its record count")
+        cur, ps = self._streams(out_host_ptr)
+        base = C.c_uint64()
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_udprecv_run(
+            self._h, self._ptr(out_host_ptr), self._ptr(out_socket), self._ptr(out_forward_ns), self._ptr(out_tag),
+            self._ptr(out_status), out_cap, self._ptr(read_host_ptr), self._ptr(reads), n_reads, C.byref(base),
+            int(until_ns), self._ptr(rx_status), self._ptr(results), self._ptr(late), late_cap,
+            self._ptr(late_count), self._ptr(first_readable_ns), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)  # torch-side consumers see the outputs (device-side ordering)
+        return base.value
+
+    def status(self, check: bool = True):
+        """srt_udprecv_status: synchronises; (flags, packets the sockets
+        processed, buffered, dropped since create).  check=True raises
+        SrtError when a flag is set."""
+        flags, a, b, d = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        err = _lib.SrtErr()
+        rc = _lib.lib().srt_udprecv_status(self._h, C.byref(flags), C.byref(a), C.byref(b), C.byref(d), C.byref(err))
+        if check or (rc != _lib.SRT_OK and not flags.value):
+            _lib.check(rc, err)
+        return flags.value, a.value, b.value, d.value
+
+    def state(self) -> np.ndarray:
+        """srt_udprecv_state: synchronises; every slot's state (UDP_STATE_DTYPE record array)."""
+        out = np.zeros(self.n_sockets, UDP_STATE_DTYPE)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_udprecv_state(self._h, out.ctypes.data if len(out) else None, C.byref(err)), err)
+        return out
+
+    def close(self):
+        if self._h:
+            _lib.lib().srt_udprecv_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def outbound_send_order(host_ptr, send_rank, late_src_host=None, late_send_rank=None):
     """The grouped send order srt_packet_batch needs, from a round's
     OutboundRelay.run outputs, with torch ops on the tensors' device.
