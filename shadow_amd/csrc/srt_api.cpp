@@ -979,8 +979,9 @@ srt_status choose_family(Create &c) {
                           ? 2u
                           : 0u;
         p->lvl_spread = !(c.knobs.lvl_spread.set && c.knobs.lvl_spread.v == 0);
-        p->lvl_lean = !c.knobs.lvl_lean.set || c.knobs.lvl_lean.v == 1 ? srt::LVL_LEAN_KEPT
-                                                                        : (uint32_t)c.knobs.lvl_lean.v & srt::LVL_LEAN_ALL;
+        p->lvl_lean = !c.knobs.lvl_lean.set || c.knobs.lvl_lean.v == 1
+                          ? srt::LVL_LEAN_KEPT | srt::LVL_LEAN_ROWS_KEPT
+                          : (uint32_t)c.knobs.lvl_lean.v & (srt::LVL_LEAN_ALL | srt::LVL_LEAN_ROWS);
         p->desc = srt::describe_level(p->kp.g, p->lvl_q, p->kp.lmax, p->V, n, c.lvl_visits, p->lvl_sym,
                                       p->d_lat16 != nullptr, p->lvl_pack != 0);
         // the packed row of a symmetric plan walks 4-byte class entries (its

@@ -39,7 +39,7 @@ struct CreateKnobs {
     Knob<int> lvl_spread;        // SRT_LVL_SPREAD: 0 = the packed row's small levels one lane group an item (A/B)
     Knob<int> lvl_lean;           // SRT_LVL_LEAN: 0 = full-row passes around every level's walk (A/B, tests); unset or 1 = the lean
                                   // stages kept (LVL_LEAN_KEPT); an even value > 1 = that mask of LVL_LEAN_* stages (A/B; 6 = without
-                                  // the wave walk of the big push levels)
+                                  // the wave walk of the big push levels; 14 = without the row stages LVL_LEAN_ROWS, 16 .. 64)
     Knob<int> fw_p1;              // SRT_FW_P1: u16/f16 phase 1, 1 = two FW steps per barrier, 0 = one (A/B)
     Knob<int> fw_emulate_ranks;   // SRT_FW_EMULATE_RANKS: rank 0's share of an N-rank schedule (measurement only)
     Knob<bool> fw_band;           // SRT_FW_BAND=1: grouped launches in banded tile order

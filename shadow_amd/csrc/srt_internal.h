@@ -55,6 +55,14 @@ constexpr uint32_t LEVEL_V_MAX = 18400;
 constexpr uint32_t LVL_LEAN_LIST = 2, LVL_LEAN_INIT = 4, LVL_LEAN_WAVE = 8;
 constexpr uint32_t LVL_LEAN_ALL = LVL_LEAN_LIST | LVL_LEAN_INIT | LVL_LEAN_WAVE;
 constexpr uint32_t LVL_LEAN_KEPT = LVL_LEAN_ALL;
+// ... and the row passes of the 4-byte-entry packed row (r14; the same knob's
+// higher bits, on where it is unset or 1): the unsettled scan reads the 4-bit
+// levels 32 vertices a 16-byte word (SCAN); a collect writes its level's member
+// list only where a later level can still push from it (DEFER); a level behind
+// an unsettled list of at most V / 4 collects over that list, not the row (PULL)
+constexpr uint32_t LVL_LEAN_SCAN = 16, LVL_LEAN_DEFER = 32, LVL_LEAN_PULL = 64;
+constexpr uint32_t LVL_LEAN_ROWS = LVL_LEAN_SCAN | LVL_LEAN_DEFER | LVL_LEAN_PULL;
+constexpr uint32_t LVL_LEAN_ROWS_KEPT = LVL_LEAN_ROWS;
 
 // In-edge of the sparse SSSP (srt_sssp.hip): the source vertex u of an
 // adjacency entry u -> v, its latency in units of g and 1 - loss rounded to f32

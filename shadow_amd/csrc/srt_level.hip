@@ -576,6 +576,12 @@ static_assert(LIST_T >= 1 && LIST_T * LIST_LPI == LIST_NT && LIST_NT <= PACK_NT,
 #endif
 constexpr uint32_t WAVE_B = SRT_WAVE_B;
 constexpr int WAVE_D = SRT_WAVE_D, WAVE_U = SRT_WAVE_U;
+// LVL_LEAN_PULL: a level behind an unsettled list of at most V / PULL_LIST_DIV
+// vertices collects over the list (a 2-byte L2 read, a key probe and a barrier a
+// step of a workgroup's threads) instead of the row (16 B of keys a quad).  4:
+// reasoned, not measured -- at a quarter of the row the list's steps are the
+// row's, each behind a global read; C3's lists are a few hundred vertices, one step.
+constexpr uint32_t PULL_LIST_DIV = 4;
 static_assert(WAVE_B >= 1 && WAVE_B <= 64, "a batch's items: a lane each");
 static_assert(WAVE_U >= 1 && WAVE_D % WAVE_U == 0, "the ring is folded in whole groups");
 // probe != nullptr: no table; probe[2 + k] = the largest level over the
@@ -631,6 +637,7 @@ __device__ __forceinline__ void level_solve_body(
     __shared__ uint64_t plan_push;
     __shared__ uint32_t plan_pull;
     __shared__ uint32_t cur[2][2];  // [level parity]: unsettled compaction, level collection
+    __shared__ uint32_t cur_w[2];   // CE4, [level parity]: a deferred member list's cursor (scan_nib)
     uint32_t *hist = reinterpret_cast<uint32_t *>(smem);  // hist[l]: end of level l in mem (l <= 31)
     uint16_t *lrow = reinterpret_cast<uint16_t *>(smem + SOLVE_HIST);
     uint32_t *prow = reinterpret_cast<uint32_t *>(smem + lds_prow_off(SOLVE_HIST, V));
@@ -653,6 +660,9 @@ __device__ __forceinline__ void level_solve_body(
         red_min[tid] = ~0ull;
         red_cnt[tid] = red_vis[tid] = 0;
     }
+    // CE4: the row passes' stages (LVL_LEAN_SCAN / DEFER / PULL of srt_internal.h; uniform)
+    const bool rows_scan = CE4 && (lean & LVL_LEAN_SCAN), rows_defer = CE4 && (lean & LVL_LEAN_DEFER);
+    const bool rows_pull = CE4 && (lean & LVL_LEAN_PULL);
     bool clean = false;  // PK: the output pass before left every key and level unreached (uniform)
     const uint32_t nrows = row_list ? row1 : row1 - row0;
     // rows dealt by a counter (row_ctr != nullptr; else statically, row k to
@@ -731,7 +741,10 @@ __device__ __forceinline__ void level_solve_body(
         // the vertices v with lrow[v] == want appended to mem[at + cur[par][ci]
         // ...) in any order: four a thread a step (one 8-B level read), one
         // LDS atomic a wave a step
-        auto compact = [&](uint16_t want, uint32_t at, uint32_t par, int ci) {
+        // (CE4, list = false: the members are counted alone -- in the wave, one
+        // LDS atomic a wave a pass -- and their range of mem stays unwritten)
+        auto compact = [&](uint16_t want, uint32_t at, uint32_t par, int ci, bool list) {
+            uint32_t acc = 0;
             for (uint32_t v4 = 4 * tid; v4 < V; v4 += 4 * nt) {
                 uint32_t fm = 0;
                 if constexpr (PK) {
@@ -776,6 +789,10 @@ __device__ __forceinline__ void level_solve_body(
                     for (uint32_t q = 0; q < 4; ++q)
                         if (v4 + q < V && lrow[v4 + q] == want) fm |= 1u << q;
                 }
+                if (CE4 && !list) {
+                    acc += (uint32_t)__popc(fm);
+                    continue;
+                }
                 uint32_t tot = 0, bel = 0;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -791,6 +808,60 @@ __device__ __forceinline__ void level_solve_body(
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                     if ((fm >> q) & 1u) mem[pos++] = (uint16_t)(v4 + q);
+            }
+            if (CE4 && !list) {
+                for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+                if (lane == 0 && acc) atomicAdd(&cur[par][ci], acc);
+            }
+        };
+        // CE4: the vertices < V whose 4-bit level is `nib` appended to mem[at + *ctr
+        // ...) in any order, a thread a 16-byte word of 32 levels: "some nibble of x
+        // equals nib" is y & y >> 1 & y >> 2 & y >> 3 & 0x11111111 of y = ~(x ^ nib in
+        // every nibble), so a word without one costs a dozen instructions and the
+        // per-vertex work runs only where a word hits.  A wave that hits takes its
+        // range by one LDS atomic (the lanes' counts summed by shuffles: a lane's own
+        // atomic on the one counter cost a level of 2,818 members 2.7 us a row).
+        // The levels' region is whole 16-byte words (solve_lds_bytes rounds it up to
+        // 16 B: V / 32 words, rounded up); the nibbles past V in the last one -- the
+        // last quad's 0xF, the padding's anything -- are masked.
+        auto scan_nib = [&](uint32_t nib, uint32_t at, uint32_t *ctr) {
+            const uint32_t pat = nib * 0x11111111u;
+            const uint4 *lev128 = reinterpret_cast<const uint4 *>(smem + pack_lev_off(V));
+            for (uint32_t w0 = (uint32_t)wv << 6; 32u * w0 < V; w0 += nt) {  // uniform in the wave
+                const uint32_t w = w0 + lane;
+                uint32_t h[4] = {0u, 0u, 0u, 0u};
+                if (32u * w < V) {
+                    const uint4 x4 = lev128[w];
+                    h[0] = x4.x, h[1] = x4.y, h[2] = x4.z, h[3] = x4.w;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        uint32_t y = ~(h[q] ^ pat);
+                        y &= y >> 1;
+                        y &= y >> 2;
+                        h[q] = y & 0x11111111u;  // bit 4 i: vertex 32 w + 8 q + i is at nib
+                    }
+                    if (32u * w + 32u > V) {  // the row's last word
+#pragma unroll
+                        for (uint32_t q = 0; q < 4; ++q) {
+                            const uint32_t b = 32u * w + 8u * q, rem = V > b ? V - b : 0u;
+                            if (rem < 8u) h[q] &= (1u << (4u * rem)) - 1u;
+                        }
+                    }
+                }
+                const uint32_t cnt = (uint32_t)(__popc(h[0]) + __popc(h[1]) + __popc(h[2]) + __popc(h[3]));
+                if (!__ballot(cnt != 0u)) continue;  // uniform
+                uint32_t incl = cnt;
+                for (int o = 1; o < 64; o <<= 1) {
+                    const uint32_t y = __shfl_up(incl, o);
+                    if (lane >= o) incl += y;
+                }
+                uint32_t b = 0;
+                if (lane == 63) b = atomicAdd(ctr, incl);
+                uint32_t pos = at + (uint32_t)__shfl(b, 63) + incl - cnt;
+#pragma unroll
+                for (uint32_t q = 0; q < 4; ++q)
+                    for (uint32_t m = h[q]; m; m &= m - 1u)
+                        mem[pos++] = (uint16_t)(32u * w + 8u * q + ((uint32_t)__builtin_ctz(m) >> 2));
             }
         };
         // 2. levels in increasing latency
@@ -817,6 +888,7 @@ __device__ __forceinline__ void level_solve_body(
                 plan_push = pm;
                 plan_pull = pl;
                 cur[par][0] = cur[par][1] = 0;
+                if constexpr (CE4) cur_w[par] = 0;
             }
             __syncthreads();
             const uint32_t T = plan_end[WCN];
@@ -841,7 +913,8 @@ __device__ __forceinline__ void level_solve_body(
 #endif
             if (plan_pull) {
                 // the unsettled vertices into mem[settled, V) (any order)
-                compact(LINF, settled, par, 0);
+                if (rows_scan) scan_nib(0xfu, settled, &cur[par][0]);
+                else compact(LINF, settled, par, 0, true);
                 __syncthreads();
             }
             LVL_TICK(0)
@@ -1245,8 +1318,47 @@ __device__ __forceinline__ void level_solve_body(
                     key[v] &= PACK_LOSS;
                     atomicAnd(&lev32[v >> 3], ~((0xfu ^ l) << (4 * (v & 7u))));
                 }
+            } else if (rows_pull && plan_pull && U <= V / PULL_LIST_DIV) {
+                // A level behind an unsettled list (mem[settled, settled + U), written before the
+                // walk): every vertex that entered the level -- pushed or pulled -- was unsettled
+                // then, so the members are the list's vertices of state 1, and a short list is
+                // walked instead of the row.  State 1 -> 0 and the level as the listed collect's;
+                // the members are packed to the list's front in place: a step's appends land
+                // below (step + 1) nt, where every read was made before the step's barrier.
+                uint32_t nx = tid < U ? mem[settled + tid] : 0u;
+                for (uint32_t b0 = 0; b0 < U; b0 += nt) {  // uniform
+                    const uint32_t m = b0 + tid, v = nx;
+                    if (m + nt < U) nx = mem[settled + m + nt];
+                    bool hit = false;
+                    if (m < U) {
+                        const uint32_t kv = key[v];
+                        hit = (kv >> 30) == 1u;
+                        if (hit) {
+                            key[v] = kv & PACK_LOSS;
+                            atomicAnd(&lev32[v >> 3], ~((0xfu ^ l) << (4 * (v & 7u))));
+                        }
+                    }
+                    __syncthreads();
+                    const uint64_t bm = __ballot(hit);
+                    if (!bm) continue;  // uniform in the wave
+                    uint32_t b = 0;
+                    if (lane == 0) b = atomicAdd(&cur[par][1], (uint32_t)__popcll(bm));
+                    b = __shfl(b, 0);
+                    if (hit) mem[settled + b + (uint32_t)__popcll(bm & below)] = (uint16_t)v;
+                }
             } else {
-                compact((uint16_t)l, settled, par, 1);
+                // A level's list is read only by a later level that pushes from it, and the plan
+                // above pushes from N_j only where nj <= U; U only falls, and right behind this
+                // collect it is V - settled - nl.  So a level of nl > V - settled - nl members can
+                // never be pushed from: its range of mem stays reserved (hist and every index as
+                // they are) and unwritten.  One that can is listed behind the barrier by the wide
+                // scan for its level.  Exact, not a heuristic: the test is the plan's own.
+                compact((uint16_t)l, settled, par, 1, !rows_defer);
+                if (rows_defer) {
+                    __syncthreads();
+                    const uint32_t nl = cur[par][1];
+                    if (nl && nl <= V - settled - nl) scan_nib(l, settled, &cur_w[par]);
+                }
             }
             __syncthreads();
             LVL_TICK(2)
