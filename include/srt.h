@@ -251,6 +251,7 @@ typedef struct {
  * three of srt_udprecv */
 enum {
     SRT_PDS_NONE = 0,
+    SRT_PDS_SND_CREATED = 1u << 1, /* the UDP send stage's: pull_out_packet made the packet (packet.minimal.h:15) */
     SRT_PDS_SND_INTERFACE_SENT = 1u << 7,
     SRT_PDS_INET_SENT = 1u << 8,
     SRT_PDS_INET_DROPPED = 1u << 9,
@@ -741,8 +742,9 @@ void srt_deliver_destroy(srt_deliver *dl);
  * The stage is exact, state included, and a pure function of each host's
  * arrival list (ready_ns, socket, priority, size, local flag), the qdisc and
  * bandwidth_up.
- * OUT OF SCOPE: how sockets produce packets (TCP/UDP buffers, retransmission)
- * and the CPU-delay model that reschedules events.  The loopback interface is
+ * OUT OF SCOPE: how sockets produce packets (TCP buffers, retransmission; UDP's
+ * send buffers are the srt_udpsend stage below, which holds this relay inside
+ * it) and the CPU-delay model that reschedules events.  The loopback interface is
  * srt_loopback below.  A local packet pushed back into the interface is
  * received as srt_deliver_run receives a forwarded one: srt_deliver_lookup, or
  * srt_deliver_lookup_flat on the device, resolves its socket.
@@ -1608,6 +1610,283 @@ srt_status srt_udprecv_state(srt_udprecv *ur, srt_udprecv_socket_state *out, srt
  * walked in device memory instead */
 uint32_t srt_udprecv_window_bytes(void);
 void srt_udprecv_destroy(srt_udprecv *ur);
+
+/* ---------------------------------------------------------- UDP send side */
+/* Where a packet's path starts: a host's UDP sockets' send buffers and its
+ * outbound relay, fused into one step per host, because the two feed each
+ * other: buffer space depends on when the relay popped each message, pop times
+ * on the qdisc and the token bucket, those on what sendmsg accepted.  The stage
+ * is srt_outbound's relay (above: qdisc, bucket, cached packet, event ids, send
+ * ranks) with UdpSocket::sendmsg (host/descriptor/socket/inet/udp.rs:327-475),
+ * pull_out_packet (:170-195), peek_next_packet_priority / has_data_to_send
+ * (:197-203), MessageBuffer (:1056-1134), the SO_SNDBUF rule (:874-899), TIOCOUTQ
+ * (:597-603, len_bytes of the state), shutdown (:767-788) and close (:229-240)
+ * inside it, and Host::get_next_packet_priority (host/host.rs:715-720, the
+ * counter starts at 1).  Its per-call outputs have srt_outbound_run's formats, so
+ * srt_sendbatch_run, srt_tracker_tx and everything behind them run on them
+ * unchanged.  It is exact, state included.
+ * State per host: everything srt_outbound keeps, next_priority, the host's own
+ * IPv4 address.  State per global socket slot (host h owns [socket_ptr[h],
+ * socket_ptr[h + 1]), srt_udprecv's and srt_tracker's slots): open, shut_wr,
+ * soft_limit, len_bytes, n_msgs, the bound (ip, port), the peer or none, at most
+ * one armed (blocked) send, a FIFO of messages {seq, priority, payload_size,
+ * local}.
+ * The events of one host in the window [previous until_ns, until_ns) run in
+ * time order.
+ *   sendmsg  srt_udp_send at time_ns, the checks in the reference's order:
+ *     1. slot >= n_sockets, not this host's, or not open: -EBADF (BAD_SOCKET);
+ *     2. shut_wr: -EPIPE (-32);
+ *     3. the destination is the given one with SRT_UDPSEND_HAS_ADDR, else the
+ *        peer, else -EDESTADDRREQ (-89);
+ *     4. len > 65507: -EMSGSIZE (-90);
+ *     5. slot not bound: NOT taken (UNBOUND).  The implicit bind of udp.rs:373-403
+ *        draws a port from the host RNG: the caller binds through
+ *        srt_udpsend_config and feeds the call again;
+ *     6. destination 127.0.0.1, or a slot bound to 127.0.0.1: NOT taken
+ *        (LOOPBACK): that traffic is srt_loopback's;
+ *     7. !(len_bytes < soft_limit): -EWOULDBLOCK (-11), or with SRT_UDPSEND_WAIT
+ *        the call is ARMED.  The limit is soft: a message is accepted whole while
+ *        len_bytes < soft_limit; a zero-length message is accepted, or refused,
+ *        by the same test and does not change len_bytes;
+ *     8. accepted: priority = next_priority++, source = the bound address with
+ *        0.0.0.0 replaced by the host's address, len_bytes += len, the message
+ *        joins the slot's FIFO, the slot the qdisc unless it is in it, an Idle
+ *        relay schedules its forward task at this time (tasks_scheduled += 1),
+ *        return_val = len, local = (destination ip == the host's address).
+ *   forward task  srt_outbound's, with total_size = payload + 28
+ *     (routing/packet.c:382, core/definitions.h:102-113).  A pop runs
+ *     pull_out_packet: len_bytes -= payload, n_msgs -= 1, the packet gets
+ *     SND_CREATED.  If the slot had no space before the pop and has space after
+ *     it, the slot turned WRITABLE at this instant: the first such time of the
+ *     call goes to d_first_writable_ns[slot] (what wakes poll / epoll waiters; an
+ *     open slot's only), and an armed send's wake-up is queued.  A packet the
+ *     relay pops and then caches has already left the send buffer.
+ *   wake-ups  the armed sends whose sockets turned writable during a forward
+ *     task are run again from check 2, after that task returns (the forward loop
+ *     keeps the interface until it blocks or empties; the woken process is a
+ *     later event of the same instant), at the task's time, in the order of the
+ *     pops that woke them.  An accepted one is an arrival at that time: an Idle
+ *     relay schedules a new forward task at the same instant (tasks_scheduled +=
+ *     1), a relay that holds a cached packet does nothing.  The result goes to
+ *     d_results[i] with complete_ns = t when the arming call is this one, else to
+ *     a late result record {seq, result}.  One armed send a socket: a second WAIT
+ *     call that finds no space meanwhile is flagged ARMED_TWICE and answered
+ *     -EWOULDBLOCK.
+ *   raw arrival  SRT_UDPSEND_RAW: a packet handed over ready-made by a socket
+ *     the stage does not model (TCP sharing the interface).  Its slot is a slot
+ *     of the host that is NOT open here (else BAD_SOCKET, not taken); len is its
+ *     total_size, priority comes from the record, SRT_UDPSEND_LOCAL from the
+ *     flags.  No buffer check, the counter untouched, always accepted; it takes
+ *     part in the qdisc and the relay like any packet and gets no SND_CREATED.  A
+ *     host with only raw arrivals produces byte for byte what srt_outbound_run
+ *     produces for the same list.
+ * Equal times at one host: the list's calls of time t in list order, then the
+ * forward task of t, then its wake-ups, then a further forward task of t if one
+ * was scheduled: srt_outbound's contract extended.
+ * LIMIT: the reference orders a running process's syscall and a forward task of
+ * one instant by event id, which the library does not own; the caller splits
+ * the window where it knows better.
+ * LIMIT: priorities drawn by other sockets of the host (TCP) inside a window:
+ * the caller sets the counter between calls (SET_NEXT_PRIORITY) and splits the
+ * window at such draws.
+ * OUT OF SCOPE: TCP and legacy_tcp, payload bytes (sizes only), the implicit bind
+ * and its RNG draw, IP_PKTINFO, the CPU-delay model, the loopback interface.
+ * ABI: additive to version 4; detect the stage by its symbols. */
+typedef struct srt_udpsend srt_udpsend;
+
+#define SRT_UDPSEND_HAS_ADDR 0x1u     /* srt_udp_send.flags: dst_ip_be / dst_port_be are given (sendto) */
+#define SRT_UDPSEND_WAIT     0x10000u /* a blocking call: neither MSG_DONTWAIT nor O_NONBLOCK */
+#define SRT_UDPSEND_RAW      0x20000u /* a ready-made packet of a socket the stage does not model */
+#define SRT_UDPSEND_LOCAL    0x40000u /* RAW only: its destination is the interface's own address */
+
+/* one sendmsg call, or one raw arrival, 40 bytes */
+typedef struct {
+    uint64_t time_ns;
+    uint64_t priority; /* RAW only */
+    uint32_t slot;
+    uint32_t len; /* the sum of the iovecs' lengths; RAW: total_size */
+    uint32_t dst_ip_be;
+    uint16_t dst_port_be;
+    uint16_t reserved;
+    uint32_t flags; /* SRT_UDPSEND_HAS_ADDR | WAIT | RAW | LOCAL */
+    uint32_t user;  /* opaque, comes back in the result */
+} srt_udp_send;
+
+#define SRT_UDPSEND_NOT_TAKEN 0u /* srt_udpsend_result.status: the call was not run; feed it again */
+#define SRT_UDPSEND_DONE      1u /* return_val and the rest are the call's result */
+#define SRT_UDPSEND_ARMED     2u /* blocked: a later call reports it in d_late_results */
+
+/* what one call returned, 40 bytes */
+typedef struct {
+    uint64_t complete_ns; /* when the call returned: its time_ns, or t for a send that blocked */
+    uint64_t priority;    /* the packet's, when accepted */
+    int64_t return_val;   /* len, or -EBADF (-9), -EWOULDBLOCK (-11), -EPIPE (-32), -EDESTADDRREQ (-89), -EMSGSIZE (-90) */
+    uint32_t status;      /* SRT_UDPSEND_NOT_TAKEN / DONE / ARMED */
+    uint32_t src_ip_be;   /* the packet's source, when accepted */
+    uint16_t src_port_be;
+    uint16_t reserved;
+    uint32_t user;
+} srt_udpsend_result;
+
+/* an armed send of an EARLIER call that completed in this one, 48 bytes */
+typedef struct {
+    uint64_t seq; /* its call's seq_base + its index */
+    srt_udpsend_result result;
+} srt_udpsend_late;
+
+#define SRT_UDPSEND_OPEN              1u /* value: send_buf_size, the soft limit as given */
+#define SRT_UDPSEND_CLOSE             2u /* new calls get -EBADF, an armed send is dropped; buffered messages still
+                                            drain through the relay (udp.rs:229-240 drops only the association,
+                                            the qdisc keeps its reference) */
+#define SRT_UDPSEND_BIND              3u /* value: ip_be | (uint64_t)port_be << 32 */
+#define SRT_UDPSEND_SET_PEER          4u /* connect: value as BIND; 0 clears the peer */
+#define SRT_UDPSEND_SET_SNDBUF        5u /* value: optval; the limit becomes min(max(optval * 2, 4096), 2^28) */
+#define SRT_UDPSEND_SHUT_WR           6u /* shutdown(SHUT_WR); ignored without a peer (ENOTCONN there) */
+#define SRT_UDPSEND_SET_NEXT_PRIORITY 7u /* per HOST: the slot field names the host, value the counter */
+
+/* one configuration step, 16 bytes */
+typedef struct {
+    uint32_t op;
+    uint32_t slot;
+    uint64_t value;
+} srt_udpsend_op;
+
+/* srt_udpsend_status flags */
+#define SRT_UDPSEND_RING_OVERFLOW        1u    /* a socket held more than ring_cap messages at the end of a call */
+#define SRT_UDPSEND_LATE_OVERFLOW        2u    /* more late packets than late_cap */
+#define SRT_UDPSEND_TIME_REGRESSION      4u    /* a call earlier than the previous until_ns: not taken */
+#define SRT_UDPSEND_OVERSIZE             8u    /* srt_outbound's rule for a packet its host's bucket can never hold */
+#define SRT_UDPSEND_AFTER_UNTIL          16u   /* a call at or after until_ns: not taken */
+#define SRT_UDPSEND_BAD_SOCKET           32u   /* -EBADF; a raw arrival: not taken */
+#define SRT_UDPSEND_UNBOUND              64u   /* not taken: bind, then feed it again */
+#define SRT_UDPSEND_LOOPBACK             128u  /* not taken: srt_loopback's traffic */
+#define SRT_UDPSEND_ARMED_TWICE          256u  /* a WAIT call while the socket has an armed one: -EWOULDBLOCK */
+#define SRT_UDPSEND_REOPEN_BUSY          512u  /* OPEN on a slot that still holds messages: ignored */
+#define SRT_UDPSEND_LATE_RESULT_OVERFLOW 1024u /* more late results than late_results_cap */
+#define SRT_UDPSEND_CALL_ORDER           2048u /* a call earlier than one before it in its host's list: not taken */
+
+/* a socket slot's state, 48 bytes; UINT64_MAX: none */
+typedef struct {
+    uint64_t len_bytes; /* TIOCOUTQ */
+    uint64_t soft_limit;
+    uint64_t armed_seq; /* the blocked send's sequence number */
+    uint32_t n_msgs;
+    uint32_t bound_ip_be;
+    uint32_t peer_ip_be;
+    uint16_t bound_port_be;
+    uint16_t peer_port_be;
+    uint8_t open;
+    uint8_t shut_wr;
+    uint8_t bound;
+    uint8_t has_peer;
+    uint8_t overflow; /* 1: the slot's ring overflowed, its host's results are invalid since */
+    uint8_t reserved0;
+    uint16_t reserved1;
+} srt_udpsend_socket_state;
+
+/* one host's state: srt_outbound_host_state's fields, then the counter */
+typedef struct {
+    uint64_t balance;
+    uint64_t last_refill_ns;
+    uint64_t task_ns;
+    uint64_t tasks_scheduled;
+    uint64_t sent_total;
+    uint64_t queue_len;
+    uint32_t cached;
+    uint32_t overflow;
+    uint64_t next_priority;
+} srt_udpsend_host_state;
+
+/* An instance for n_hosts hosts on the plan's device and stream, or, with plan
+ * == NULL, host-only: every array argument named d_ is then a HOST pointer and
+ * the calls complete before they return.  Both forms run the same step and
+ * agree byte for byte.  socket_ptr as for srt_udprecv_create; host_ip_be and
+ * bw_up_bytes_per_s: HOST pointers, n_hosts entries; qdisc: SRT_QDISC_*.
+ * ring_cap is the number of messages a socket may hold ACROSS calls; inside a
+ * call a socket's queue is as long as the call's list makes it.  A host's
+ * slots * (ring_cap + 1) and late_cap_hint are below 2^31 (SRT_ERR_INVALID);
+ * late_cap_hint sizes nothing yet.  Memory of the instance, in bytes:
+ *   64 + n_hosts * 112 + n_sockets * (88 + 4 + (ring_cap + 1) * 32)
+ *      + (n_hosts + 1) * 4 + max(n_sockets + n_hosts, 1024) * 16 + n_calls * 32
+ * (the call-wide words; per host its state record; per slot its state record,
+ * its place in its host's qdisc array and its ring of messages with one spare
+ * element for a woken send of an earlier call; socket_ptr; the configuration
+ * steps of one launch; a 32-byte staged record per call of the largest n_calls
+ * seen; each part rounded up to a multiple of 16, and 16 spare bytes), on the
+ * device.  The staged records are the one thing that grows: the first run, and
+ * a run with more calls than any before, wait for the stream and reallocate
+ * them; no other run allocates or waits.  Buckets start full, last refill at
+ * 0, next_priority at 1.  Destroy the instance before its plan. */
+srt_status srt_udpsend_create(srt_plan *plan, uint32_t n_hosts, const uint32_t *socket_ptr, const uint32_t *host_ip_be,
+                              const uint64_t *bw_up_bytes_per_s, uint32_t qdisc, uint32_t ring_cap,
+                              uint32_t late_cap_hint, srt_udpsend **out, srt_err *err);
+
+/* Configuration between runs: n steps (HOST pointer), applied in list order,
+ * as srt_udprecv_config applies its own (every call first waits for the
+ * stream: batch a window's steps into one call).  A slot >= n_sockets (a host
+ * >= n_hosts for SET_NEXT_PRIORITY) or an unknown op returns SRT_ERR_INVALID
+ * and changes NOTHING.  OPEN gives an empty, unbound, unconnected socket with
+ * the limit as given; on a slot that still holds messages (open, or closed and
+ * still draining) it is ignored and flagged REOPEN_BUSY.  Every other socket
+ * step on a slot that is not open is ignored.  A limit set below len_bytes
+ * leaves the socket without space until pops drain it. */
+srt_status srt_udpsend_config(srt_udpsend *us, const srt_udpsend_op *ops, uint64_t n, srt_err *err);
+
+/* One scheduling window.  d_calls: n_calls (< 2^31) records grouped by host
+ * through d_call_host_ptr (n_hosts + 1 entries), each host's in issue order
+ * with nondecreasing time_ns inside [previous until_ns, until_ns).  Every call
+ * runs at its time_ns and every forward task with a time < until_ns runs.
+ * Outputs: d_results[i] for every call; d_pds_status / d_send_ns / d_send_rank
+ * [n_calls], d_late (late_cap records) / *d_late_count and *seq_base exactly as
+ * srt_outbound_run defines them, indexed by call: a call that was not accepted
+ * keeps status 0 and UINT64_MAX, an accepted one is a packet under the
+ * sequence number *seq_base + its index (a UDP packet's status has SND_CREATED
+ * from its pop on); d_late_results (late_results_cap records, any order) /
+ * *d_late_results_count: the armed sends of earlier calls that completed;
+ * d_first_writable_ns[slot] for every slot: see above, else UINT64_MAX.
+ * Conditions, collected for srt_udpsend_status; every write is range-checked
+ * first, a flagged call never writes out of bounds:
+ *   RING_OVERFLOW    the newest messages beyond ring_cap are lost, the slot and
+ *                    its host are marked and only that host's results are invalid;
+ *   LATE_OVERFLOW, LATE_RESULT_OVERFLOW   the records beyond the cap are lost;
+ *   TIME_REGRESSION, CALL_ORDER, AFTER_UNTIL   the call is not taken;
+ *   OVERSIZE         srt_outbound's rule;
+ *   BAD_SOCKET, UNBOUND, LOOPBACK, ARMED_TWICE   as above.
+ * Asynchronous on the plan's stream, two launches: it does not wait for the
+ * device, except where the staged records grow (srt_udpsend_create). */
+srt_status srt_udpsend_run(srt_udpsend *us, const uint32_t *d_call_host_ptr, const srt_udp_send *d_calls,
+                           uint64_t n_calls, uint64_t until_ns, uint64_t bootstrap_end_ns,
+                           srt_udpsend_result *d_results, uint32_t *d_pds_status, uint64_t *d_send_ns,
+                           uint64_t *d_send_rank, srt_outbound_late *d_late, uint32_t late_cap, uint32_t *d_late_count,
+                           srt_udpsend_late *d_late_results, uint32_t late_results_cap, uint32_t *d_late_results_count,
+                           uint64_t *d_first_writable_ns, uint64_t *seq_base, srt_err *err);
+
+/* Synchronises the stream.  *flags (may be NULL): the SRT_UDPSEND_* conditions
+ * met since the last status call (then cleared); *n_pending: packets still in
+ * the stage after the last run; *n_accepted / *n_would_block / *n_armed: calls
+ * accepted (raw arrivals and woken sends included), answered -EWOULDBLOCK, and
+ * armed, since create.  SRT_ERR_INVALID, with a message that names every flag
+ * set, when any was; else SRT_OK. */
+srt_status srt_udpsend_status(srt_udpsend *us, uint32_t *flags, uint64_t *n_pending, uint64_t *n_accepted,
+                              uint64_t *n_would_block, uint64_t *n_armed, srt_err *err);
+
+/* Synchronises and copies every host's state to hosts[n_hosts] and every slot's
+ * to socks[n_sockets] (HOST pointers; either may be NULL). */
+srt_status srt_udpsend_state(srt_udpsend *us, srt_udpsend_host_state *hosts, srt_udpsend_socket_state *socks,
+                             srt_err *err);
+
+/* srt_outbound_cached_seq for this stage: d_seq[h] = the sequence number of the
+ * packet host h's relay holds cached after the last run, or UINT64_MAX.
+ * Asynchronous on the plan's stream.  For srt_tracker_tx. */
+srt_status srt_udpsend_cached_seq(srt_udpsend *us, uint64_t *d_seq, srt_err *err);
+
+/* The LDS a workgroup (one wave, 64 hosts) of the step kernel asks for, in
+ * bytes: 1536 staged calls of 32 bytes (a wave whose hosts' calls are more is
+ * walked in device memory instead), then 320 slot state records of 88 bytes and
+ * their 320 qdisc entries (a wave whose hosts own more slots keeps them in
+ * device memory): 78,592, two workgroups a CU. */
+uint32_t srt_udpsend_window_bytes(void);
+void srt_udpsend_destroy(srt_udpsend *us);
 
 /* ---------------------------------------------------- IP assignment (a10) */
 /* IpAssignment<u32> (src/main/network/graph/mod.rs:352-420): IPv4 address ->

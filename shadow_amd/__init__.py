@@ -10,8 +10,8 @@ runs in libsrt.so on the GPU.  There is no CPU fallback.
 from ._lib import SrtError, init, init_async, lib  # noqa: F401
 from .graph import (IpAssignment, NetGraphError, NetworkGraph, PathProperties, PathTable,  # noqa: F401
                     RoutingInfo, generate_routing_info, load_network_graph)
-from .plan import LoopbackRelay, PcapCapture, Tracker, UdpReceive  # noqa: F401
+from .plan import LoopbackRelay, PcapCapture, Tracker, UdpReceive, UdpSend  # noqa: F401
 
 __all__ = ["NetworkGraph", "PathProperties", "PathTable", "RoutingInfo", "IpAssignment", "NetGraphError",
-           "SrtError", "Tracker", "LoopbackRelay", "PcapCapture", "UdpReceive", "generate_routing_info",
+           "SrtError", "Tracker", "LoopbackRelay", "PcapCapture", "UdpReceive", "UdpSend", "generate_routing_info",
            "load_network_graph", "lib", "init", "init_async"]

@@ -61,6 +61,16 @@ UDPRECV_OPEN, UDPRECV_CLOSE, UDPRECV_SET_PEER, UDPRECV_SET_RCVBUF = 1, 2, 3, 4
 UDPRECV_RING_OVERFLOW, UDPRECV_LATE_OVERFLOW, UDPRECV_NOTE_OVERRUN, UDPRECV_BAD_SOCKET = 1, 2, 4, 8
 UDPRECV_READ_ORDER, UDPRECV_ARMED_TWICE = 16, 32
 UDPRECV_MARK_RING, UDPRECV_MARK_NOTE = 1, 2
+# the UDP send stage: its packet status bit, srt_udp_send flags, srt_udpsend_result status, srt_udpsend_op ops,
+# srt_udpsend_status flags
+PDS_SND_CREATED = 1 << 1
+UDPSEND_HAS_ADDR, UDPSEND_WAIT, UDPSEND_RAW, UDPSEND_LOCAL = 0x1, 0x10000, 0x20000, 0x40000
+UDPSEND_NOT_TAKEN, UDPSEND_DONE, UDPSEND_ARMED = 0, 1, 2
+UDPSEND_OPEN, UDPSEND_CLOSE, UDPSEND_BIND, UDPSEND_SET_PEER, UDPSEND_SET_SNDBUF, UDPSEND_SHUT_WR = 1, 2, 3, 4, 5, 6
+UDPSEND_SET_NEXT_PRIORITY = 7
+UDPSEND_RING_OVERFLOW, UDPSEND_LATE_OVERFLOW, UDPSEND_TIME_REGRESSION, UDPSEND_OVERSIZE = 1, 2, 4, 8
+UDPSEND_AFTER_UNTIL, UDPSEND_BAD_SOCKET, UDPSEND_UNBOUND, UDPSEND_LOOPBACK = 16, 32, 64, 128
+UDPSEND_ARMED_TWICE, UDPSEND_REOPEN_BUSY, UDPSEND_LATE_RESULT_OVERFLOW, UDPSEND_CALL_ORDER = 256, 512, 1024, 2048
 
 
 class SrtErr(C.Structure):
@@ -247,6 +257,16 @@ SIGNATURES = {
     "srt_udprecv_state": (C.c_int, [_vp, _vp, _errp]),
     "srt_udprecv_window_bytes": (C.c_uint32, []),
     "srt_udprecv_destroy": (None, [_vp]),
+    "srt_udpsend_create": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp),
+                                     _errp]),
+    "srt_udpsend_config": (C.c_int, [_vp, _vp, C.c_uint64, _errp]),
+    "srt_udpsend_run": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.c_uint32,
+                                  _vp, _vp, C.c_uint32, _vp, _vp, _u64p, _errp]),
+    "srt_udpsend_status": (C.c_int, [_vp, _u32p, _u64p, _u64p, _u64p, _u64p, _errp]),
+    "srt_udpsend_state": (C.c_int, [_vp, _vp, _vp, _errp]),
+    "srt_udpsend_cached_seq": (C.c_int, [_vp, _vp, _errp]),
+    "srt_udpsend_window_bytes": (C.c_uint32, []),
+    "srt_udpsend_destroy": (None, [_vp]),
     "srt_routing_info_build": (C.c_int, [C.POINTER(SrtCsr), _u32p, C.c_uint32, C.c_int, C.POINTER(SrtOpts),
                                          C.POINTER(_vp), _errp]),
     "srt_routing_info_from_plan": (C.c_int, [_vp, C.POINTER(_vp), _errp]),

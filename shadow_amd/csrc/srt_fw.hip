@@ -3098,6 +3098,7 @@ hipError_t preload_kernels() {
     if (e == hipSuccess) e = preload_loopback();
     if (e == hipSuccess) e = preload_pcap();
     if (e == hipSuccess) e = preload_udprecv();
+    if (e == hipSuccess) e = preload_udpsend();
     return e;
 }
 

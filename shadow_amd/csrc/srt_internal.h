@@ -510,6 +510,7 @@ hipError_t preload_tracker();
 hipError_t preload_loopback();
 hipError_t preload_pcap();
 hipError_t preload_udprecv();
+hipError_t preload_udpsend();
 // srt_deliver.hip: the instance's association table as the next launch on its plan's stream sees it
 // (rebuilt on the host and uploaded on the stream when the associations have changed since the last
 // upload: srt_deliver_run's own path), with the instance's plan (nullptr: host-only) and n_hosts

@@ -1303,6 +1303,151 @@ class UdpReceive:
             pass
 
 
+UDP_SEND_DTYPE = np.dtype([("time_ns", "<u8"), ("priority", "<u8"), ("slot", "<u4"), ("len", "<u4"),
+                           ("dst_ip_be", "<u4"), ("dst_port_be", "<u2"), ("reserved", "<u2"), ("flags", "<u4"),
+                           ("user", "<u4")])
+UDPSEND_RESULT_DTYPE = np.dtype([("complete_ns", "<u8"), ("priority", "<u8"), ("return_val", "<i8"), ("status", "<u4"),
+                                 ("src_ip_be", "<u4"), ("src_port_be", "<u2"), ("reserved", "<u2"), ("user", "<u4")])
+UDPSEND_LATE_DTYPE = np.dtype([("seq", "<u8"), ("result", UDPSEND_RESULT_DTYPE)])
+UDPSEND_OP_DTYPE = np.dtype([("op", "<u4"), ("slot", "<u4"), ("value", "<u8")])
+UDPSEND_SOCKET_STATE_DTYPE = np.dtype([("len_bytes", "<u8"), ("soft_limit", "<u8"), ("armed_seq", "<u8"),
+                                       ("n_msgs", "<u4"), ("bound_ip_be", "<u4"), ("peer_ip_be", "<u4"),
+                                       ("bound_port_be", "<u2"), ("peer_port_be", "<u2"), ("open", "u1"),
+                                       ("shut_wr", "u1"), ("bound", "u1"), ("has_peer", "u1"), ("overflow", "u1"),
+                                       ("reserved0", "u1"), ("reserved1", "<u2")])
+UDPSEND_HOST_STATE_DTYPE = np.dtype([(k, "<u8") for k in (
+    "balance", "last_refill_ns", "task_ns", "tasks_scheduled", "sent_total", "queue_len")] + [
+        ("cached", "<u4"), ("overflow", "<u4"), ("next_priority", "<u8")])
+
+
+class UdpSend:
+    """srt_udpsend: every host's UDP send buffers and its outbound relay in one
+    fused step (UdpSocket::sendmsg, pull_out_packet, MessageBuffer, the
+    SO_SNDBUF rule, shutdown, close, Host::get_next_packet_priority, and
+    OutboundRelay's qdisc, bucket and relay loop), a host a lane.  socket_ptr
+    [n_hosts+1] gives every host its global slots, the ones UdpReceive and
+    Tracker use.  config() opens, binds, connects, resizes, shuts and closes
+    sockets and sets a host's priority counter (UDPSEND_OP_DTYPE, on the host);
+    run() takes a window's sendmsg calls (UDP_SEND_DTYPE) and answers them
+    (UDPSEND_RESULT_DTYPE, UDPSEND_LATE_DTYPE) beside OutboundRelay.run's
+    outputs, which SendBatch.run takes as they are.
+
+    Bound to a RoutingPlan (arrays are torch CUDA tensors of its device, the
+    calls are asynchronous on its stream; closing the plan closes it), or
+    host-only with plan=None (arrays are numpy arrays, the same step on the
+    CPU)."""
+
+    def __init__(self, plan: Optional[RoutingPlan], socket_ptr, host_ip_be, bw_up_bytes_per_s, qdisc: int,
+                 ring_cap: int, late_cap_hint: int = 0):
+        self.plan = plan
+        sp = np.ascontiguousarray(socket_ptr, np.uint32).reshape(-1)
+        if len(sp) < 1:
+            raise ValueError("UdpSend: socket_ptr needs n_hosts + 1 entries")
+        self.n_hosts, self.n_sockets = len(sp) - 1, int(sp[-1])
+        ip = np.ascontiguousarray(host_ip_be, np.uint32).reshape(-1)
+        bw = np.ascontiguousarray(bw_up_bytes_per_s, np.uint64).reshape(-1)
+        if len(ip) != self.n_hosts or len(bw) != self.n_hosts:
+            raise ValueError("UdpSend: host_ip_be and bw_up_bytes_per_s need n_hosts entries")
+        self._h = C.c_void_p()
+        if plan is not None:
+            _bind_to_plan(self, plan)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_udpsend_create(plan.handle if plan is not None else None, self.n_hosts,
+                                                 sp.ctypes.data, ip.ctypes.data if len(ip) else None,
+                                                 bw.ctypes.data if len(bw) else None, int(qdisc), int(ring_cap),
+                                                 int(late_cap_hint), C.byref(self._h), C.byref(err)), err)
+
+    _ptr = staticmethod(InboundRouter._ptr)
+    _nbytes = staticmethod(SendBatch._nbytes)
+    _streams = FlightStore._streams
+
+    @staticmethod
+    def window_bytes() -> int:
+        """srt_udpsend_window_bytes: the LDS a wave of the step kernel asks for"""
+        return int(_lib.lib().srt_udpsend_window_bytes())
+
+    def config(self, ops):
+        """srt_udpsend_config: UDPSEND_OP_DTYPE records (a host numpy array), applied in
+        list order.  Raises SrtError, and changes nothing, for a bad slot or op."""
+        a = np.ascontiguousarray(ops, UDPSEND_OP_DTYPE).reshape(-1)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_udpsend_config(self._h, a.ctypes.data if len(a) else None, len(a), C.byref(err)), err)
+
+    def run(self, call_host_ptr, calls, until_ns: int, bootstrap_end_ns: int, results, status, send_ns, send_rank,
+            late, late_count, late_results, late_results_count, first_writable_ns) -> int:
+        """srt_udpsend_run.  call_host_ptr int32/uint32 [n_hosts+1]; calls, a
+        uint8 view of 40-byte srt_udp_send records grouped by host.  Outputs:
+        results, a uint8 buffer of 40-byte srt_udpsend_result records, one a
+        call; status int32/uint32, send_ns and send_rank int64/uint64, [n_calls]
+        each, late (32-byte srt_outbound_late records) and late_count exactly
+        as OutboundRelay.run writes them; late_results, a uint8 buffer of
+        48-byte srt_udpsend_late records with late_results_count a 1-element
+        int32/uint32; first_writable_ns int64/uint64 [n_sockets].  Returns the
+        calls' sequence base.  Device form: enqueue only (status() synchronises)."""
+        n_calls = self._nbytes(calls) // 40
+        late_cap = self._nbytes(late) // 32
+        late_res_cap = self._nbytes(late_results) // 48
+        if self._nbytes(call_host_ptr) < 4 * (self.n_hosts + 1) or self._nbytes(results) < 40 * n_calls or \
+                self._nbytes(status) < 4 * n_calls or self._nbytes(send_ns) < 8 * n_calls or \
+                self._nbytes(send_rank) < 8 * n_calls or self._nbytes(first_writable_ns) < 8 * self.n_sockets or \
+                (late_cap and late_count is None) or (late_res_cap and late_results_count is None):
+            raise ValueError("UdpSend.run: an array is smaller than its record count")
+        cur, ps = self._streams(call_host_ptr)
+        base = C.c_uint64()
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_udpsend_run(
+            self._h, self._ptr(call_host_ptr), self._ptr(calls), n_calls, int(until_ns), int(bootstrap_end_ns),
+            self._ptr(results), self._ptr(status), self._ptr(send_ns), self._ptr(send_rank), self._ptr(late), late_cap,
+            self._ptr(late_count), self._ptr(late_results), late_res_cap, self._ptr(late_results_count),
+            self._ptr(first_writable_ns), C.byref(base), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)  # torch-side consumers see the outputs (device-side ordering)
+        return base.value
+
+    def status(self, check: bool = True):
+        """srt_udpsend_status: synchronises; (flags, packets pending, calls
+        accepted, answered -EWOULDBLOCK, armed since create).  check=True raises
+        SrtError when a flag is set."""
+        flags = C.c_uint32()
+        n = [C.c_uint64() for _ in range(4)]
+        err = _lib.SrtErr()
+        rc = _lib.lib().srt_udpsend_status(self._h, C.byref(flags), *[C.byref(x) for x in n], C.byref(err))
+        if check or (rc != _lib.SRT_OK and not flags.value):
+            _lib.check(rc, err)
+        return (flags.value,) + tuple(x.value for x in n)
+
+    def state(self):
+        """srt_udpsend_state: synchronises; (hosts, UDPSEND_HOST_STATE_DTYPE; slots, UDPSEND_SOCKET_STATE_DTYPE)."""
+        hosts = np.zeros(self.n_hosts, UDPSEND_HOST_STATE_DTYPE)
+        socks = np.zeros(self.n_sockets, UDPSEND_SOCKET_STATE_DTYPE)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_udpsend_state(self._h, hosts.ctypes.data if len(hosts) else None,
+                                                socks.ctypes.data if len(socks) else None, C.byref(err)), err)
+        return hosts, socks
+
+    def cached_seq(self, out):
+        """srt_udpsend_cached_seq: out int64/uint64 [n_hosts], as OutboundRelay.cached_seq.  Device form: enqueue only."""
+        if self._nbytes(out) < 8 * self.n_hosts:
+            raise ValueError("UdpSend.cached_seq: out is smaller than n_hosts")
+        cur, ps = self._streams(out) if self.n_hosts else (None, None)
+        err = _lib.SrtErr()
+        _lib.check(_lib.lib().srt_udpsend_cached_seq(self._h, self._ptr(out), C.byref(err)), err)
+        if cur is not None:
+            cur.wait_stream(ps)
+        return out
+
+    def close(self):
+        if self._h:
+            _lib.lib().srt_udpsend_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def outbound_send_order(host_ptr, send_rank, late_src_host=None, late_send_rank=None):
     """The grouped send order srt_packet_batch needs, from a round's
     OutboundRelay.run outputs, with torch ops on the tensors' device.
